@@ -14,6 +14,14 @@ per-GPU work fixed); `value` aggregates clusters-ready/sec over all ranks.
 
 Run:  python bench.py --gpus N --steps K --warmup W
 The driver launches N>1 via torch.distributed.run, one rank per GPU.
+
+A plain run only sets up, warms up, times the K steps and prints the result
+line. `--dump-outputs DIR` additionally writes what the last timed step
+computed (the status the operator published for every RayCluster when it
+turned Ready, one row per cluster in name order) as DIR/<name>.npy so two
+builds can be compared output for output. `--full` is where measurements
+beyond the headline figure belong; today every figure in the result line
+comes from the timed steps themselves, so `--full` adds nothing yet.
 """
 from __future__ import annotations
 
@@ -35,8 +43,10 @@ def rss_mb() -> float:
 
 
 def run_step(cp, n_clusters: int, workers_per_cluster: int, gpus_per_worker: int,
-             step_idx: int, rank: int):
-    """Create → all Ready → delete → drained. Returns per-step stats."""
+             step_idx: int, rank: int, capture: bool = False):
+    """Create → all Ready → delete → drained. Returns per-step stats; with
+    `capture` also each cluster's status dict as published when it turned
+    Ready (kept as is; converting it is left until after the timed region)."""
     from kuberay_amd.models import RayCluster
     from kuberay_amd.testing import simple_raycluster
     from kuberay_amd.utils import constants as C
@@ -58,6 +68,7 @@ def run_step(cp, n_clusters: int, workers_per_cluster: int, gpus_per_worker: int
     t_create_done = time.perf_counter()
 
     ready_latency = {}
+    ready_status = {}
     pending = set(create_times)
     deadline = time.monotonic() + 600
     while pending and time.monotonic() < deadline:
@@ -68,6 +79,8 @@ def run_step(cp, n_clusters: int, workers_per_cluster: int, gpus_per_worker: int
         name = obj["metadata"]["name"]
         if name in pending and obj.get("status", {}).get("state") == "ready":
             ready_latency[name] = time.perf_counter() - create_times[name]
+            if capture:
+                ready_status[name] = dict(obj["status"])
             pending.discard(name)
     watcher.stop()
     if pending:
@@ -92,7 +105,57 @@ def run_step(cp, n_clusters: int, workers_per_cluster: int, gpus_per_worker: int
         "p99_ready_s": lat[int(len(lat) * 0.99) - 1] if len(lat) > 1 else lat[0],
         "rss_mb_at_scale": rss_at_scale,
         "pods_at_scale": n_pods,
+        "ready_status": ready_status,
     }
+
+
+OUTPUT_COLUMNS = (
+    "state_is_ready", "desired_cpu", "desired_memory_bytes", "desired_gpu",
+    "ready_worker_replicas", "available_worker_replicas",
+    "desired_worker_replicas", "min_worker_replicas", "max_worker_replicas",
+    "observed_generation", "conditions_true", "n_endpoints",
+)
+
+
+def status_row(st: dict) -> tuple:
+    """The OUTPUT_COLUMNS values of one RayCluster status, as floats.
+    Timestamps, pod-name suffixes and IPs are left out — only what the
+    reconciler derives from the spec and the pod set is kept."""
+    from kuberay_amd.utils.quantity import parse_quantity
+    return (
+        float(st.get("state") == "ready"),
+        float(parse_quantity(st.get("desiredCPU"))),
+        float(parse_quantity(st.get("desiredMemory"))),
+        float(parse_quantity(st.get("desiredGPU"))),
+        float(st.get("readyWorkerReplicas", 0)),
+        float(st.get("availableWorkerReplicas", 0)),
+        float(st.get("desiredWorkerReplicas", 0)),
+        float(st.get("minWorkerReplicas", 0)),
+        float(st.get("maxWorkerReplicas", 0)),
+        float(st.get("observedGeneration") or 0),
+        float(sum(c.get("status") == "True"
+                  for c in st.get("conditions") or [])),
+        float(len(st.get("endpoints") or {})),
+    )
+
+
+def dump_outputs(out_dir: str, step_stats: dict, rank: int, world: int) -> None:
+    """Write the last timed step's outputs as float64 .npy arrays: one entry
+    per RayCluster, ordered by cluster name (names are a pure function of
+    rank/step/index, so the order is identical from run to run)."""
+    import numpy as np
+
+    statuses = step_stats["ready_status"]
+    table = np.array([status_row(statuses[n]) for n in sorted(statuses)],
+                     dtype=np.float64)
+    arrays = {name: np.ascontiguousarray(table[:, i])
+              for i, name in enumerate(OUTPUT_COLUMNS)}
+    arrays["pods_at_scale"] = np.array([step_stats["pods_at_scale"]],
+                                       dtype=np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    suffix = f"_rank{rank}" if world > 1 else ""
+    for name, arr in arrays.items():
+        np.save(os.path.join(out_dir, f"{name}{suffix}.npy"), arr)
 
 
 def main() -> int:
@@ -105,6 +168,13 @@ def main() -> int:
     parser.add_argument("--gpus-per-worker", type=int, default=1)
     parser.add_argument("--controller-workers", type=int, default=0,
                         help="0 = auto: min(8, cores/world), >=2")
+    parser.add_argument("--dump-outputs", metavar="DIR", default=None,
+                        help="after the timed steps, write the last step's "
+                             "outputs as DIR/<name>.npy")
+    parser.add_argument("--full", action="store_true",
+                        help="also run measurements beyond the headline "
+                             "figure (none today: every reported figure "
+                             "comes from the timed steps)")
     args = parser.parse_args()
 
     rank = int(os.environ.get("RANK", "0"))
@@ -162,8 +232,10 @@ def main() -> int:
         t0 = time.perf_counter()
         stats = []
         for k in range(args.steps):
-            stats.append(run_step(cp, args.clusters, args.workers_per_cluster,
-                                  args.gpus_per_worker, step_idx=k, rank=rank))
+            stats.append(run_step(
+                cp, args.clusters, args.workers_per_cluster,
+                args.gpus_per_worker, step_idx=k, rank=rank,
+                capture=bool(args.dump_outputs) and k == args.steps - 1))
         barrier()
         t1 = time.perf_counter()
     finally:
@@ -171,6 +243,8 @@ def main() -> int:
         cp.stop()
 
     elapsed = t1 - t0
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, stats[-1], rank, world)
     # MAX elapsed over ranks (slowest rank defines the job), SUM of work
     if dist is not None:
         te = torch.tensor([elapsed], dtype=torch.float64,
