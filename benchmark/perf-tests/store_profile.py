@@ -1,0 +1,205 @@
+#!/usr/bin/env python3
+"""Where the control plane's CPU goes in the object store, per call site.
+
+Runs N bench-style steps (bench.py's run_step: create the RayClusters, wait
+for Ready, delete, drain) with the store's entry points and its JSON calls
+wrapped in ``time.thread_time()`` and prints each site's share of the
+process CPU. The benchmark is one GIL-bound core of host work (the GPU idles
+during it), so this table — not a kernel profile — is what says where a
+store change pays.
+
+    python benchmark/perf-tests/store_profile.py --clusters 200 --steps 3
+
+``--root DIR`` profiles another checkout of this repository (for a
+before/after on the same host); every site is looked up by name and skipped
+where a checkout does not have it. CPU-only: no GPU is touched.
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import os
+import sys
+import threading
+import time
+from collections import defaultdict
+
+
+class Sites:
+    """Per-site thread-CPU accumulators (inclusive time)."""
+
+    def __init__(self) -> None:
+        self.cpu = defaultdict(float)
+        self.calls = defaultdict(int)
+        self.lock = threading.Lock()
+        self.tls = threading.local()
+
+    def add(self, site: str, dt: float) -> None:
+        with self.lock:
+            self.cpu[site] += dt
+            self.calls[site] += 1
+
+    def wrap(self, site: str, fn, group: str = None):
+        """Time ``fn`` under ``site``; with ``group``, the outermost call of
+        any function of that group is also charged to the group (nested
+        calls, e.g. update() inside mutate_status(), are not counted twice)."""
+        sites = self
+        clock = time.thread_time
+
+        def timed(*args, **kwargs):
+            tls = sites.tls
+            depth = getattr(tls, "depth", None)
+            if depth is None:
+                depth = tls.depth = defaultdict(int)
+            outer = group is not None and depth[group] == 0
+            if group is not None:
+                depth[group] += 1
+            t0 = clock()
+            try:
+                return fn(*args, **kwargs)
+            finally:
+                dt = clock() - t0
+                if group is not None:
+                    depth[group] -= 1
+                sites.add(site, dt)
+                if outer:
+                    sites.add(group, dt)
+        timed.__wrapped__ = fn
+        return timed
+
+
+STORE_VERBS = ("create", "update", "delete", "get", "try_get", "list",
+               "list_pod_views", "patch_merge", "mutate_status",
+               "events_since")
+
+
+def instrument(sites: Sites) -> None:
+    from kuberay_amd.kube import store as store_mod
+    server_cls = store_mod.InMemoryApiServer
+    for verb in STORE_VERBS:
+        fn = getattr(server_cls, verb, None)
+        if fn is not None:
+            setattr(server_cls, verb, sites.wrap(
+                f"InMemoryApiServer.{verb}", fn, group="store layer (all verbs)"))
+
+    # the watch-history serialization happens inside _notify through the
+    # json module itself; tell it apart from every other json.dumps caller
+    notify = server_cls._notify
+    real_dumps = json.dumps
+    timed_hist = sites.wrap("json.dumps in _notify (watch history)", real_dumps)
+    timed_other = sites.wrap("json.dumps elsewhere", real_dumps)
+
+    def dumps(*args, **kwargs):
+        if getattr(sites.tls, "in_notify", 0):
+            return timed_hist(*args, **kwargs)
+        return timed_other(*args, **kwargs)
+
+    def notify_flagged(self, *args, **kwargs):
+        sites.tls.in_notify = getattr(sites.tls, "in_notify", 0) + 1
+        try:
+            return notify(self, *args, **kwargs)
+        finally:
+            sites.tls.in_notify -= 1
+
+    try:
+        from kuberay_amd.kube import native as native_mod
+    except ImportError:
+        native_mod = None
+    # native.py binds json.dumps / json.loads at import: wrap its own names
+    # before json.dumps is replaced below
+    if native_mod is not None:
+        native_mod._loads = sites.wrap(
+            "json.loads of stored blobs (NativeBackend)", native_mod._loads)
+        native_mod._dumps = sites.wrap(
+            "json.dumps in NativeBackend.put", native_mod._dumps)
+        backend_cls = native_mod.NativeBackend
+        for name in ("put", "put_status", "fetch", "remove", "list",
+                     "list_views", "peek", "history_since"):
+            fn = getattr(backend_cls, name, None)
+            if fn is not None:
+                setattr(backend_cls, name,
+                        sites.wrap(f"NativeBackend.{name}", fn))
+    json.dumps = dumps
+    server_cls._notify = sites.wrap("InMemoryApiServer._notify", notify_flagged)
+
+
+def main() -> int:
+    parser = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
+    parser.add_argument("--clusters", type=int, default=200)
+    parser.add_argument("--steps", type=int, default=3)
+    parser.add_argument("--warmup", type=int, default=1)
+    parser.add_argument("--workers-per-cluster", type=int, default=3)
+    parser.add_argument("--controller-workers", type=int, default=4)
+    parser.add_argument("--root", default=None,
+                        help="checkout to profile (default: this one)")
+    parser.add_argument("--json", action="store_true",
+                        help="print the table as one JSON line as well")
+    args = parser.parse_args()
+
+    root = os.path.abspath(args.root or os.path.join(
+        os.path.dirname(os.path.abspath(__file__)), "..", ".."))
+    sys.path.insert(0, root)
+    import bench  # the checkout's own step definition
+    from kuberay_amd.testing import ControlPlane
+
+    sites = Sites()
+    instrument(sites)
+
+    cp = ControlPlane(kubelet_delay=0.0, workers=args.controller_workers,
+                      record_events=False, requeue_seconds=3600,
+                      poll_seconds=1.0, kubelet_executors=2)
+    cp.start()
+    try:
+        for w in range(args.warmup):
+            bench.run_step(cp, args.clusters, args.workers_per_cluster, 1,
+                           step_idx=-1 - w, rank=0)
+        with sites.lock:
+            sites.cpu.clear()
+            sites.calls.clear()
+        cpu0, wall0 = time.process_time(), time.perf_counter()
+        for k in range(args.steps):
+            bench.run_step(cp, args.clusters, args.workers_per_cluster, 1,
+                           step_idx=k, rank=0)
+        cpu, wall = time.process_time() - cpu0, time.perf_counter() - wall0
+        stats = getattr(cp.server._backend, "stats", None)
+        engine_stats = stats() if stats else None
+    finally:
+        cp.stop()
+
+    with sites.lock:
+        snapshot = {s: (sites.cpu[s], sites.calls[s]) for s in sites.cpu}
+    put = snapshot.get("NativeBackend.put")
+    if put:
+        inner = snapshot.get("json.dumps in NativeBackend.put", (0.0, 0))
+        snapshot["NativeBackend.put minus its json.dumps"] = (
+            put[0] - inner[0], put[1])
+
+    total_clusters = args.clusters * args.steps
+    print(f"root: {root}")
+    print(f"backend: {cp.server.backend_name}   clusters/step: {args.clusters}"
+          f"   steps: {args.steps}")
+    print(f"wall {wall:.2f} s   process CPU {cpu:.2f} s   "
+          f"{total_clusters / wall:.1f} clusters/s   "
+          f"{cpu / total_clusters * 1e3:.2f} ms CPU/cluster")
+    print()
+    print(f"| {'where':<52} | {'share':>6} | {'calls':>7} | {'CPU s':>7} | "
+          f"{'us/call':>7} |")
+    print(f"|{'-' * 54}|{'-' * 8}|{'-' * 9}|{'-' * 9}|{'-' * 9}|")
+    for site, (t, n) in sorted(snapshot.items(), key=lambda kv: -kv[1][0]):
+        print(f"| {site:<52} | {100 * t / cpu:5.1f}% | {n:7d} | {t:7.3f} | "
+              f"{(t / n * 1e6 if n else 0):7.1f} |")
+    if engine_stats:
+        print()
+        print("engine counters (whole run, warm-up included): "
+              + ", ".join(f"{k}={v}" for k, v in engine_stats.items()))
+    if args.json:
+        print(json.dumps({
+            "root": root, "wall_s": wall, "cpu_s": cpu,
+            "clusters_per_s": total_clusters / wall,
+            "sites": {s: {"cpu_s": t, "calls": n, "share": t / cpu}
+                      for s, (t, n) in snapshot.items()}}))
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

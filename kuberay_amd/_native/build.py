@@ -3,7 +3,8 @@ live next to the sources so it travels to GPU boxes with the repo snapshot).
 
 Extensions:
   * gpuhealth  — HIP/gfx950 on-device health probes (gpuhealth.hip)
-  * engine     — C++ control-plane core: object cache + indices (engine.cpp)
+  * engine     — C++ control-plane core: object cache + indices + native
+                 JSON encoding (engine.cpp bindings over store_core.hpp)
 
 Build: ``python -m kuberay_amd._native.build`` or ``__graft_entry__.build()``.
 """
@@ -30,8 +31,11 @@ def _pybind11_includes() -> list:
             f"-I{sysconfig.get_paths()['include']}"]
 
 
-def _needs_rebuild(src: Path, out: Path) -> bool:
-    return not out.exists() or src.stat().st_mtime > out.stat().st_mtime
+def _needs_rebuild(src: Path, out: Path, *deps: Path) -> bool:
+    if not out.exists():
+        return True
+    built = out.stat().st_mtime
+    return any(p.stat().st_mtime > built for p in (src, *deps) if p.exists())
 
 
 def build_gpuhealth(force: bool = False) -> Path:
@@ -53,7 +57,7 @@ def build_engine(force: bool = False) -> Path:
     out = HERE / f"engine{_ext_suffix()}"
     if not src.exists():
         return out
-    if not force and not _needs_rebuild(src, out):
+    if not force and not _needs_rebuild(src, out, HERE / "store_core.hpp"):
         return out
     cxx = os.environ.get("CXX", "g++")
     cmd = [

@@ -3,274 +3,586 @@
 // The reconcile path of the operator is bound by its object cache: at the
 // 500-cluster soak the cache holds ~2500 objects (2000 pods),
 // and a Python dict-tree store pays deep copies + GC pressure + RSS for all
-// of them. This backend keeps every object as ONE compact JSON blob in C++
-// heap with label / kind / owner-uid indexes beside it, plus precomputed
-// "pod views" (the 9 fields the RayCluster reconciler actually reads per
-// pod per reconcile) so the hot loop never materializes a pod at all.
+// of them. This backend keeps every object as compact JSON in C++ heap with
+// label / kind / owner-uid indexes beside it, plus precomputed "pod views"
+// (the 9 fields the RayCluster reconciler actually reads per pod per
+// reconcile) so the hot loop never materializes a pod at all.
 //
-// Semantics live in python (kuberay_amd/kube/store.py InMemoryApiServer);
-// this is pure storage + indexing. Thread-safe via an internal mutex —
-// callers do NOT need the python-side lock for reads.
+// The engine owns the encoding too: put_object / put_status walk the Python
+// dict tree once, write compact JSON straight into the sections the store
+// keeps (store_core.hpp), pull the index fields and the pod view out of the
+// same tree and append the watch-history entry — one call per write, no
+// Python str in between. A status write re-encodes metadata + status only.
+//
+// Semantics live in python (kuberay_amd/kube/store.py InMemoryApiServer).
+// This file is the pybind11 half: bindings, the PyObject encoder and field
+// extraction. Everything that needs no Python is in store_core.hpp.
+// Thread-safe: the core has its own mutex, which is never held while a
+// Python object is created or destroyed.
 
 #include <pybind11/pybind11.h>
 #include <pybind11/stl.h>
 
-#include <algorithm>
-#include <cstdint>
-#include <mutex>
+#include <cmath>
+#include <cstdio>
 #include <optional>
 #include <string>
-#include <unordered_map>
 #include <unordered_set>
 #include <vector>
 
+#include "store_core.hpp"
+
 namespace py = pybind11;
+using namespace kuberay_store;
 
 namespace {
 
-struct PodViewData {
-  std::string name, ns, phase, deletion_ts, pod_ip, restart_policy, creation_ts;
-  bool ready = false;
-  bool terminated = false;
-};
+// Thrown when the fast path meets anything it does not reproduce exactly;
+// the caller then takes the json.dumps + put(blob) path, which behaves (and
+// fails) as it always did.
+struct Decline {};
 
-struct Entry {
-  std::string kind, ns, name;
-  std::string blob;  // compact JSON of the whole object
-  std::string rv;
-  std::vector<std::pair<std::string, std::string>> labels;
-  std::vector<std::string> owner_uids;
-  bool has_view = false;
-  PodViewData view;
-};
+// Nesting the encoder follows before it declines (json.dumps goes on to the
+// interpreter's recursion limit and reports circular structures itself).
+constexpr int kMaxDepth = 128;
 
-inline std::string make_key(const std::string& kind, const std::string& ns,
-                            const std::string& name) {
-  std::string k;
-  k.reserve(kind.size() + ns.size() + name.size() + 2);
-  k += kind; k += '\x1f'; k += ns; k += '\x1f'; k += name;
-  return k;
+struct Keys {
+  PyObject *metadata, *status, *spec, *labels, *ownerReferences, *uid,
+      *resourceVersion, *finalizers, *deletionTimestamp, *name, *ns, *phase,
+      *podIP, *restartPolicy, *creationTimestamp, *conditions, *type,
+      *containers, *containerStatuses, *state, *terminated;
+};
+Keys K;
+
+void init_keys() {
+  auto mk = [](const char* s) { return PyUnicode_InternFromString(s); };
+  K.metadata = mk("metadata"); K.status = mk("status"); K.spec = mk("spec");
+  K.labels = mk("labels"); K.ownerReferences = mk("ownerReferences");
+  K.uid = mk("uid"); K.resourceVersion = mk("resourceVersion");
+  K.finalizers = mk("finalizers");
+  K.deletionTimestamp = mk("deletionTimestamp");
+  K.name = mk("name"); K.ns = mk("namespace"); K.phase = mk("phase");
+  K.podIP = mk("podIP"); K.restartPolicy = mk("restartPolicy");
+  K.creationTimestamp = mk("creationTimestamp");
+  K.conditions = mk("conditions"); K.type = mk("type");
+  K.containers = mk("containers");
+  K.containerStatuses = mk("containerStatuses"); K.state = mk("state");
+  K.terminated = mk("terminated");
 }
 
-inline std::string label_key(const std::string& kind, const std::string& k,
-                             const std::string& v) {
-  std::string out;
-  out.reserve(kind.size() + k.size() + v.size() + 2);
-  out += kind; out += '\x1f'; out += k; out += '\x1f'; out += v;
-  return out;
+// ---------------------------------------------------------------------------
+// encoder: exact dict / list / str / bool / None / int64 / finite float
+// ---------------------------------------------------------------------------
+
+void encode_str(PyObject* s, std::string& out) {
+  Py_ssize_t n = 0;
+  const char* p = PyUnicode_AsUTF8AndSize(s, &n);
+  if (p == nullptr) {  // lone surrogate
+    PyErr_Clear();
+    throw Decline{};
+  }
+  static const char* hex = "0123456789abcdef";
+  out.push_back('"');
+  const char* run = p;
+  const char* end = p + n;
+  for (const char* c = p; c < end; ++c) {
+    const unsigned char ch = static_cast<unsigned char>(*c);
+    if (ch >= 0x20 && ch != '"' && ch != '\\') continue;
+    out.append(run, c - run);
+    run = c + 1;
+    switch (ch) {
+      case '"': out += "\\\""; break;
+      case '\\': out += "\\\\"; break;
+      case '\n': out += "\\n"; break;
+      case '\r': out += "\\r"; break;
+      case '\t': out += "\\t"; break;
+      case '\b': out += "\\b"; break;
+      case '\f': out += "\\f"; break;
+      default:
+        out += "\\u00";
+        out.push_back(hex[ch >> 4]);
+        out.push_back(hex[ch & 0xf]);
+    }
+  }
+  out.append(run, end - run);
+  out.push_back('"');
+}
+
+void encode(PyObject* o, std::string& out, int depth) {
+  if (PyUnicode_CheckExact(o)) {
+    encode_str(o, out);
+  } else if (PyDict_CheckExact(o)) {
+    if (depth >= kMaxDepth) throw Decline{};
+    out.push_back('{');
+    Py_ssize_t pos = 0;
+    PyObject *k, *v;
+    bool first = true;
+    while (PyDict_Next(o, &pos, &k, &v)) {
+      if (!PyUnicode_CheckExact(k)) throw Decline{};
+      if (!first) out.push_back(',');
+      first = false;
+      encode_str(k, out);
+      out.push_back(':');
+      encode(v, out, depth + 1);
+    }
+    out.push_back('}');
+  } else if (PyList_CheckExact(o)) {
+    if (depth >= kMaxDepth) throw Decline{};
+    out.push_back('[');
+    const Py_ssize_t n = PyList_GET_SIZE(o);
+    for (Py_ssize_t i = 0; i < n; ++i) {
+      if (i) out.push_back(',');
+      encode(PyList_GET_ITEM(o, i), out, depth + 1);
+    }
+    out.push_back(']');
+  } else if (o == Py_None) {
+    out += "null";
+  } else if (o == Py_True) {
+    out += "true";
+  } else if (o == Py_False) {
+    out += "false";
+  } else if (PyLong_CheckExact(o)) {
+    int overflow = 0;
+    const long long v = PyLong_AsLongLongAndOverflow(o, &overflow);
+    if (overflow) throw Decline{};
+    char buf[24];
+    out.append(buf, std::snprintf(buf, sizeof buf, "%lld", v));
+  } else if (PyFloat_CheckExact(o)) {
+    const double d = PyFloat_AS_DOUBLE(o);
+    if (!std::isfinite(d)) throw Decline{};
+    char* s = PyOS_double_to_string(d, 'r', 0, Py_DTSF_ADD_DOT_0, nullptr);
+    if (s == nullptr) {
+      PyErr_Clear();
+      throw Decline{};
+    }
+    out += s;
+    PyMem_Free(s);
+  } else {
+    throw Decline{};  // tuple, subclass, anything else
+  }
+}
+
+// ---------------------------------------------------------------------------
+// field extraction — the python expressions of NativeBackend.put /
+// compute_pod_view, on exact builtin types; anything else declines
+// ---------------------------------------------------------------------------
+
+// d.get(key) on an exact dict (borrowed, nullptr when missing)
+PyObject* dget(PyObject* d, PyObject* key) {
+  PyObject* v = PyDict_GetItemWithError(d, key);
+  if (v == nullptr && PyErr_Occurred()) {
+    PyErr_Clear();
+    throw Decline{};
+  }
+  return v;
+}
+
+bool truthy(PyObject* o) {
+  if (o == nullptr || o == Py_None) return false;
+  const int t = PyObject_IsTrue(o);
+  if (t < 0) {
+    PyErr_Clear();
+    throw Decline{};
+  }
+  return t != 0;
+}
+
+// `o or {}` that must then answer .get(): nullptr stands for the empty dict
+PyObject* dict_or_empty(PyObject* o) {
+  if (!truthy(o)) return nullptr;
+  if (!PyDict_CheckExact(o)) throw Decline{};
+  return o;
+}
+
+// `o or []` that is then iterated: nullptr stands for the empty list
+PyObject* list_or_empty(PyObject* o) {
+  if (!truthy(o)) return nullptr;
+  if (!PyList_CheckExact(o)) throw Decline{};
+  return o;
+}
+
+std::string to_utf8(PyObject* s) {
+  if (!PyUnicode_CheckExact(s)) throw Decline{};
+  Py_ssize_t n = 0;
+  const char* p = PyUnicode_AsUTF8AndSize(s, &n);
+  if (p == nullptr) {
+    PyErr_Clear();
+    throw Decline{};
+  }
+  return std::string(p, n);
+}
+
+// `d.get(key) or ""` bound for a std::string
+std::string str_or_empty(PyObject* d, PyObject* key) {
+  PyObject* v = d ? dget(d, key) : nullptr;
+  if (!truthy(v)) return std::string();
+  return to_utf8(v);
+}
+
+// `d.get(key, dflt)` bound for a std::string (None is a TypeError there)
+std::string str_default(PyObject* d, PyObject* key, const char* dflt) {
+  PyObject* v = d ? dget(d, key) : nullptr;
+  if (v == nullptr) return dflt;
+  return to_utf8(v);
+}
+
+bool str_equals(PyObject* o, const char* lit) {
+  return o != nullptr && PyUnicode_CheckExact(o) &&
+         PyUnicode_CompareWithASCIIString(o, lit) == 0;
+}
+
+// obj.get("metadata", {}): nullptr when missing; anything but a dict declines
+PyObject* metadata_of(PyObject* obj) {
+  PyObject* meta = dget(obj, K.metadata);
+  if (meta != nullptr && !PyDict_CheckExact(meta)) throw Decline{};
+  return meta;
+}
+
+void extract_peek(PyObject* meta, Peek& p) {
+  p.rv = str_default(meta, K.resourceVersion, "");
+  PyObject* uid = meta ? dget(meta, K.uid) : nullptr;
+  p.uid = (uid && PyUnicode_CheckExact(uid)) ? to_utf8(uid) : std::string();
+  p.has_finalizers = truthy(meta ? dget(meta, K.finalizers) : nullptr);
+  p.deletion_ts = str_or_empty(meta, K.deletionTimestamp);
+}
+
+void extract_indexes(PyObject* meta, Fields& f) {
+  if (PyObject* labels = dict_or_empty(meta ? dget(meta, K.labels) : nullptr)) {
+    Py_ssize_t pos = 0;
+    PyObject *k, *v;
+    while (PyDict_Next(labels, &pos, &k, &v)) {
+      f.labels.emplace_back(to_utf8(k), to_utf8(v));
+    }
+  }
+  if (PyObject* refs =
+          list_or_empty(meta ? dget(meta, K.ownerReferences) : nullptr)) {
+    const Py_ssize_t n = PyList_GET_SIZE(refs);
+    for (Py_ssize_t i = 0; i < n; ++i) {
+      PyObject* ref = PyList_GET_ITEM(refs, i);
+      if (!PyDict_CheckExact(ref)) throw Decline{};
+      PyObject* uid = dget(ref, K.uid);
+      if (truthy(uid)) f.owner_uids.push_back(to_utf8(uid));
+    }
+  }
+}
+
+// compute_pod_view (kube/store.py), field for field
+void extract_view(PyObject* obj, PyObject* meta, PodViewData& v) {
+  PyObject* status = dict_or_empty(dget(obj, K.status));
+  PyObject* spec = dict_or_empty(dget(obj, K.spec));
+  v.name = str_default(meta, K.name, "");
+  v.ns = str_default(meta, K.ns, "default");
+  v.phase = str_or_empty(status, K.phase);
+  v.deletion_ts = str_or_empty(meta, K.deletionTimestamp);
+  v.pod_ip = str_or_empty(status, K.podIP);
+  v.restart_policy = str_or_empty(spec, K.restartPolicy);
+  v.creation_ts = str_or_empty(meta, K.creationTimestamp);
+  v.ready = false;
+  if (PyObject* conds =
+          list_or_empty(status ? dget(status, K.conditions) : nullptr)) {
+    const Py_ssize_t n = PyList_GET_SIZE(conds);
+    for (Py_ssize_t i = 0; i < n; ++i) {
+      PyObject* c = PyList_GET_ITEM(conds, i);
+      if (!PyDict_CheckExact(c)) throw Decline{};
+      if (str_equals(dget(c, K.type), "Ready") &&
+          str_equals(dget(c, K.status), "True")) {
+        v.ready = true;
+        break;
+      }
+    }
+  }
+  v.terminated = false;
+  PyObject* containers = spec ? dget(spec, K.containers) : nullptr;
+  if (!truthy(containers)) return;
+  if (!PyList_CheckExact(containers)) throw Decline{};
+  PyObject* first = PyList_GET_ITEM(containers, 0);
+  if (!PyDict_CheckExact(first)) throw Decline{};
+  PyObject* ray_name = dget(first, K.name);
+  if (ray_name == nullptr) ray_name = Py_None;
+  PyObject* cstats =
+      list_or_empty(status ? dget(status, K.containerStatuses) : nullptr);
+  if (cstats == nullptr) return;
+  const Py_ssize_t n = PyList_GET_SIZE(cstats);
+  for (Py_ssize_t i = 0; i < n; ++i) {
+    PyObject* cs = PyList_GET_ITEM(cstats, i);
+    if (!PyDict_CheckExact(cs)) throw Decline{};
+    PyObject* name = dget(cs, K.name);
+    if (name == nullptr) name = Py_None;
+    const int eq = PyObject_RichCompareBool(name, ray_name, Py_EQ);
+    if (eq < 0) {
+      PyErr_Clear();
+      throw Decline{};
+    }
+    if (!eq) continue;
+    PyObject* state = dict_or_empty(dget(cs, K.state));
+    if (state != nullptr && truthy(dget(state, K.terminated))) {
+      v.terminated = true;
+      break;
+    }
+  }
+}
+
+Section make_section(const std::string& scratch) {
+  return std::make_shared<const std::string>(scratch.data(), scratch.size());
+}
+
+py::bytes to_bytes(const Blob& b) {
+  const size_t n = b.size();
+  PyObject* out = PyBytes_FromStringAndSize(nullptr, static_cast<Py_ssize_t>(n));
+  if (out == nullptr) throw py::error_already_set();
+  b.write(PyBytes_AS_STRING(out));
+  return py::reinterpret_steal<py::bytes>(out);
 }
 
 class NativeStore {
  public:
-  void put(const std::string& kind, const std::string& ns,
-           const std::string& name, const std::string& blob,
-           const std::string& rv,
-           const std::vector<std::pair<std::string, std::string>>& labels,
-           const std::vector<std::string>& owner_uids,
-           const std::optional<PodViewData>& view) {
-    std::lock_guard<std::mutex> g(mu_);
-    const std::string key = make_key(kind, ns, name);
-    auto it = objects_.find(key);
-    if (it != objects_.end()) {
-      index_remove(key, it->second);
+  explicit NativeStore(size_t history_capacity) : core_(history_capacity) {}
+
+  // Full write of a Python object tree. Returns whether the key was new, or
+  // None when the fast path declines (nothing is written then).
+  py::object put_object(const std::string& kind, const std::string& ns,
+                        const std::string& name, py::handle obj,
+                        const std::optional<std::string>& event_type) {
+    static thread_local std::string rest, meta_s, status_s;
+    rest.clear(); meta_s.clear(); status_s.clear();
+    Blob blob;
+    Fields f;
+    try {
+      PyObject* o = obj.ptr();
+      if (!PyDict_CheckExact(o)) throw Decline{};
+      bool has_meta = false, has_status = false;
+      Py_ssize_t pos = 0;
+      PyObject *k, *v;
+      while (PyDict_Next(o, &pos, &k, &v)) {
+        if (!PyUnicode_CheckExact(k)) throw Decline{};
+        if (PyUnicode_CompareWithASCIIString(k, "metadata") == 0) {
+          encode(v, meta_s, 1);
+          has_meta = true;
+        } else if (PyUnicode_CompareWithASCIIString(k, "status") == 0) {
+          encode(v, status_s, 1);
+          has_status = true;
+        } else {
+          if (!rest.empty()) rest.push_back(',');
+          encode_str(k, rest);
+          rest.push_back(':');
+          encode(v, rest, 1);
+        }
+      }
+      PyObject* meta = metadata_of(o);
+      Peek p;
+      extract_peek(meta, p);
+      f.rv = std::move(p.rv); f.uid = std::move(p.uid);
+      f.deletion_ts = std::move(p.deletion_ts);
+      f.has_finalizers = p.has_finalizers;
+      extract_indexes(meta, f);
+      if (kind == "Pod") {
+        extract_view(o, meta, f.view);
+        f.has_view = true;
+      }
+      blob.rest = make_section(rest);
+      if (has_meta) blob.meta = make_section(meta_s);
+      if (has_status) blob.status = make_section(status_s);
+    } catch (const Decline&) {
+      core_.note_fallback();
+      return py::none();
     }
-    Entry e;
-    e.kind = kind; e.ns = ns; e.name = name;
-    e.blob = blob; e.rv = rv;
-    e.labels = labels; e.owner_uids = owner_uids;
-    if (view) { e.has_view = true; e.view = *view; }
-    index_add(key, e);
-    objects_[key] = std::move(e);
+    core_.note_encode(true, rest.size() + meta_s.size() + status_s.size());
+    const bool is_new = core_.put(kind, ns, name, std::move(blob), std::move(f),
+                                  event_type ? event_type->c_str() : nullptr);
+    return py::bool_(is_new);
+  }
+
+  // Status write: metadata + status re-encoded, everything else kept.
+  // Returns True, or None when it cannot splice (missing key, blob entry,
+  // or a tree the fast path declines) and the caller must do a full put.
+  py::object put_status(const std::string& kind, const std::string& ns,
+                        const std::string& name, py::handle obj,
+                        const std::optional<std::string>& event_type) {
+    static thread_local std::string meta_s, status_s;
+    meta_s.clear(); status_s.clear();
+    Section meta_sec, status_sec;
+    Peek p;
+    PodViewData view;
+    const bool is_pod = kind == "Pod";
+    try {
+      PyObject* o = obj.ptr();
+      if (!PyDict_CheckExact(o)) throw Decline{};
+      PyObject* meta = metadata_of(o);
+      if (meta != nullptr) {
+        encode(meta, meta_s, 1);
+        meta_sec = make_section(meta_s);
+      }
+      if (PyObject* status = dget(o, K.status)) {
+        encode(status, status_s, 1);
+        status_sec = make_section(status_s);
+      }
+      extract_peek(meta, p);
+      if (is_pod) extract_view(o, meta, view);
+    } catch (const Decline&) {
+      return py::none();
+    }
+    if (!core_.put_status(kind, ns, name, std::move(meta_sec),
+                          std::move(status_sec), std::move(p), is_pod,
+                          std::move(view),
+                          event_type ? event_type->c_str() : nullptr)) {
+      return py::none();
+    }
+    core_.note_encode(false, meta_s.size() + status_s.size());
+    return py::bool_(true);
+  }
+
+  // Write of a ready-made blob (the path for trees the encoder declines).
+  bool put(const std::string& kind, const std::string& ns,
+           const std::string& name, const std::string& blob,
+           const std::string& rv, const LabelList& labels,
+           const std::vector<std::string>& owner_uids,
+           const std::optional<PodViewData>& view,
+           const std::optional<std::string>& event_type,
+           const std::string& uid, bool has_finalizers,
+           const std::string& deletion_ts) {
+    Blob b;
+    b.rest = std::make_shared<const std::string>(blob);
+    b.whole = true;
+    Fields f;
+    f.rv = rv; f.uid = uid; f.deletion_ts = deletion_ts;
+    f.has_finalizers = has_finalizers;
+    f.labels = labels; f.owner_uids = owner_uids;
+    if (view) { f.has_view = true; f.view = *view; }
+    return core_.put(kind, ns, name, std::move(b), std::move(f),
+                     event_type ? event_type->c_str() : nullptr);
   }
 
   std::optional<py::bytes> fetch(const std::string& kind, const std::string& ns,
-                                 const std::string& name) const {
-    std::lock_guard<std::mutex> g(mu_);
-    auto it = objects_.find(make_key(kind, ns, name));
-    if (it == objects_.end()) return std::nullopt;
-    return py::bytes(it->second.blob);
+                                 const std::string& name) {
+    std::optional<Blob> b = core_.fetch(kind, ns, name);
+    if (!b) return std::nullopt;
+    core_.note_assembled(1, b->size());
+    return to_bytes(*b);
   }
 
   std::optional<std::string> rv(const std::string& kind, const std::string& ns,
                                 const std::string& name) const {
-    std::lock_guard<std::mutex> g(mu_);
-    auto it = objects_.find(make_key(kind, ns, name));
-    if (it == objects_.end()) return std::nullopt;
-    return it->second.rv;
+    return core_.rv(kind, ns, name);
+  }
+
+  py::object peek(const std::string& kind, const std::string& ns,
+                  const std::string& name) const {
+    std::optional<Peek> p = core_.peek(kind, ns, name);
+    if (!p) return py::none();
+    return py::make_tuple(p->rv, p->uid, p->has_finalizers, p->deletion_ts);
   }
 
   bool contains(const std::string& kind, const std::string& ns,
                 const std::string& name) const {
-    std::lock_guard<std::mutex> g(mu_);
-    return objects_.count(make_key(kind, ns, name)) != 0;
+    return core_.contains(kind, ns, name);
   }
 
   std::optional<py::bytes> remove(const std::string& kind, const std::string& ns,
-                                  const std::string& name) {
-    std::lock_guard<std::mutex> g(mu_);
-    auto it = objects_.find(make_key(kind, ns, name));
-    if (it == objects_.end()) return std::nullopt;
-    py::bytes out(it->second.blob);
-    index_remove(it->first, it->second);
-    objects_.erase(it);
-    return out;
+                                  const std::string& name,
+                                  std::optional<int64_t> event_rv) {
+    std::optional<Blob> b = core_.remove(kind, ns, name, event_rv);
+    if (!b) return std::nullopt;
+    core_.note_assembled(1, b->size());
+    return to_bytes(*b);
   }
 
-  std::vector<py::bytes> list_blobs(
-      const std::string& kind, const std::optional<std::string>& ns,
-      const std::vector<std::pair<std::string, std::string>>& selector) const {
-    std::lock_guard<std::mutex> g(mu_);
-    std::vector<const Entry*> entries = select(kind, ns, selector);
-    std::sort(entries.begin(), entries.end(), [](const Entry* a, const Entry* b) {
-      return std::tie(a->ns, a->name) < std::tie(b->ns, b->name);
-    });
+  std::vector<py::bytes> list_blobs(const std::string& kind,
+                                    const std::optional<std::string>& ns,
+                                    const LabelList& selector) {
+    std::vector<Blob> blobs = core_.list(kind, ns, selector);
     std::vector<py::bytes> out;
-    out.reserve(entries.size());
-    for (const Entry* e : entries) out.emplace_back(e->blob);
+    out.reserve(blobs.size());
+    size_t bytes = 0;
+    for (const Blob& b : blobs) {
+      bytes += b.size();
+      out.push_back(to_bytes(b));
+    }
+    core_.note_assembled(blobs.size(), bytes);
     return out;
   }
 
   // Returns per-pod view tuples:
   // (name, ns, labels, phase, ready, deletion_ts, pod_ip, restart_policy,
   //  terminated, creation_ts)
-  py::list list_views(
-      const std::optional<std::string>& ns,
-      const std::vector<std::pair<std::string, std::string>>& selector) const {
-    std::vector<const Entry*> entries;
-    {
-      std::lock_guard<std::mutex> g(mu_);
-      entries = select("Pod", ns, selector);
-      std::sort(entries.begin(), entries.end(), [](const Entry* a, const Entry* b) {
-        return std::tie(a->ns, a->name) < std::tie(b->ns, b->name);
-      });
-      // build python objects while still holding the lock (entries point
-      // into the map; cheap enough at view granularity)
-      py::list out;
-      for (const Entry* e : entries) {
-        if (!e->has_view) continue;
-        py::dict labels;
-        for (const auto& kv : e->labels) {
-          labels[py::str(kv.first)] = py::str(kv.second);
-        }
-        out.append(py::make_tuple(
-            e->view.name, e->view.ns, labels, e->view.phase, e->view.ready,
-            e->view.deletion_ts, e->view.pod_ip, e->view.restart_policy,
-            e->view.terminated, e->view.creation_ts));
+  py::list list_views(const std::optional<std::string>& ns,
+                      const LabelList& selector) const {
+    std::vector<ViewRow> rows = core_.list_views(ns, selector);
+    py::list out;
+    for (const ViewRow& r : rows) {
+      py::dict labels;
+      for (const auto& kv : r.labels) {
+        labels[py::str(kv.first)] = py::str(kv.second);
       }
-      return out;
+      out.append(py::make_tuple(
+          r.view.name, r.view.ns, labels, r.view.phase, r.view.ready,
+          r.view.deletion_ts, r.view.pod_ip, r.view.restart_policy,
+          r.view.terminated, r.view.creation_ts));
     }
+    return out;
   }
 
   std::vector<py::tuple> dependents(const std::string& uid) const {
-    std::lock_guard<std::mutex> g(mu_);
     std::vector<py::tuple> out;
-    auto it = owner_index_.find(uid);
-    if (it == owner_index_.end()) return out;
-    for (const auto& key : it->second) {
-      auto oit = objects_.find(key);
-      if (oit != objects_.end()) {
-        out.push_back(py::make_tuple(oit->second.kind, oit->second.ns,
-                                     oit->second.name));
-      }
+    for (const auto& t : core_.dependents(uid)) {
+      out.push_back(py::make_tuple(std::get<0>(t), std::get<1>(t),
+                                   std::get<2>(t)));
     }
     return out;
   }
 
-  void drop_owner(const std::string& uid) {
-    std::lock_guard<std::mutex> g(mu_);
-    owner_index_.erase(uid);
+  void drop_owner(const std::string& uid) { core_.drop_owner(uid); }
+  size_t count(const std::string& kind) const { return core_.count(kind); }
+  size_t total_bytes() const { return core_.total_bytes(); }
+
+  // [(event type, bytes, rv override or None)] oldest first, or None when
+  // `rv` is older than the ring can replay.
+  py::object history_since(int64_t rv,
+                           const std::optional<std::unordered_set<std::string>>&
+                               kinds) {
+    std::optional<std::vector<HistoryItem>> items =
+        core_.history_since(rv, kinds ? &*kinds : nullptr);
+    if (!items) return py::none();
+    py::list out;
+    size_t bytes = 0;
+    for (const HistoryItem& h : *items) {
+      bytes += h.blob.size();
+      py::object override_rv = py::none();
+      if (h.rv_override) override_rv = py::int_(*h.rv_override);
+      out.append(py::make_tuple(h.event_type, to_bytes(h.blob), override_rv));
+    }
+    core_.note_assembled(items->size(), bytes);
+    return out;
   }
 
-  size_t count(const std::string& kind) const {
-    std::lock_guard<std::mutex> g(mu_);
-    auto it = kind_index_.find(kind);
-    return it == kind_index_.end() ? 0 : it->second.size();
+  void history_reset(int64_t base, size_t capacity) {
+    core_.history_reset(base, capacity);
   }
 
-  size_t total_bytes() const {
-    std::lock_guard<std::mutex> g(mu_);
-    size_t n = 0;
-    for (const auto& kv : objects_) n += kv.second.blob.size();
-    return n;
+  std::vector<int64_t> history_rvs() const { return core_.history_rvs(); }
+
+  py::dict stats() const {
+    const Stats s = core_.stats();
+    py::dict d;
+    d["full_encodes"] = s.full_encodes;
+    d["partial_encodes"] = s.partial_encodes;
+    d["bytes_encoded"] = s.bytes_encoded;
+    d["blobs_assembled"] = s.blobs_assembled;
+    d["bytes_assembled"] = s.bytes_assembled;
+    d["fallbacks"] = s.fallbacks;
+    d["history_appends"] = s.history_appends;
+    return d;
   }
 
  private:
-  std::vector<const Entry*> select(
-      const std::string& kind, const std::optional<std::string>& ns,
-      const std::vector<std::pair<std::string, std::string>>& selector) const {
-    std::vector<const Entry*> out;
-    const std::unordered_set<std::string>* keys = nullptr;
-    std::unordered_set<std::string> intersection;
-    if (!selector.empty()) {
-      // start from the smallest label bucket
-      const std::unordered_set<std::string>* smallest = nullptr;
-      for (const auto& kv : selector) {
-        auto it = label_index_.find(label_key(kind, kv.first, kv.second));
-        if (it == label_index_.end()) return out;  // empty bucket -> no match
-        if (smallest == nullptr || it->second.size() < smallest->size()) {
-          smallest = &it->second;
-        }
-      }
-      keys = smallest;
-    } else {
-      auto it = kind_index_.find(kind);
-      if (it == kind_index_.end()) return out;
-      keys = &it->second;
-    }
-    for (const auto& key : *keys) {
-      auto oit = objects_.find(key);
-      if (oit == objects_.end()) continue;
-      const Entry& e = oit->second;
-      if (e.kind != kind) continue;
-      if (ns && e.ns != *ns) continue;
-      bool ok = true;
-      for (const auto& kv : selector) {
-        bool found = false;
-        for (const auto& lv : e.labels) {
-          if (lv.first == kv.first && lv.second == kv.second) { found = true; break; }
-        }
-        if (!found) { ok = false; break; }
-      }
-      if (ok) out.push_back(&e);
-    }
-    return out;
-  }
-
-  void index_add(const std::string& key, const Entry& e) {
-    kind_index_[e.kind].insert(key);
-    for (const auto& kv : e.labels) {
-      label_index_[label_key(e.kind, kv.first, kv.second)].insert(key);
-    }
-    for (const auto& uid : e.owner_uids) owner_index_[uid].insert(key);
-  }
-
-  void index_remove(const std::string& key, const Entry& e) {
-    auto kit = kind_index_.find(e.kind);
-    if (kit != kind_index_.end()) kit->second.erase(key);
-    for (const auto& kv : e.labels) {
-      auto lit = label_index_.find(label_key(e.kind, kv.first, kv.second));
-      if (lit != label_index_.end()) {
-        lit->second.erase(key);
-        if (lit->second.empty()) label_index_.erase(lit);
-      }
-    }
-    for (const auto& uid : e.owner_uids) {
-      auto oit = owner_index_.find(uid);
-      if (oit != owner_index_.end()) oit->second.erase(key);
-    }
-  }
-
-  mutable std::mutex mu_;
-  std::unordered_map<std::string, Entry> objects_;
-  std::unordered_map<std::string, std::unordered_set<std::string>> kind_index_;
-  std::unordered_map<std::string, std::unordered_set<std::string>> label_index_;
-  std::unordered_map<std::string, std::unordered_set<std::string>> owner_index_;
+  StoreCore core_;
 };
 
 }  // namespace
 
 PYBIND11_MODULE(engine, m) {
-  m.doc() = "kuberay-amd native object store (C++ blobs + indexes + pod views)";
+  m.doc() = "kuberay-amd native object store (C++ sections + indexes + pod "
+            "views + watch history, native JSON encoding)";
+  init_keys();
 
   py::class_<PodViewData>(m, "PodViewData")
       .def(py::init<>())
@@ -285,21 +597,36 @@ PYBIND11_MODULE(engine, m) {
       .def_readwrite("terminated", &PodViewData::terminated);
 
   py::class_<NativeStore>(m, "NativeStore")
-      .def(py::init<>())
+      .def(py::init<size_t>(), py::arg("history_capacity") = 1024)
+      .def("put_object", &NativeStore::put_object, py::arg("kind"),
+           py::arg("ns"), py::arg("name"), py::arg("obj"),
+           py::arg("event_type") = std::nullopt)
+      .def("put_status", &NativeStore::put_status, py::arg("kind"),
+           py::arg("ns"), py::arg("name"), py::arg("obj"),
+           py::arg("event_type") = std::nullopt)
       .def("put", &NativeStore::put, py::arg("kind"), py::arg("ns"),
            py::arg("name"), py::arg("blob"), py::arg("rv"), py::arg("labels"),
-           py::arg("owner_uids"), py::arg("view") = std::nullopt)
+           py::arg("owner_uids"), py::arg("view") = std::nullopt,
+           py::arg("event_type") = std::nullopt, py::arg("uid") = "",
+           py::arg("has_finalizers") = false, py::arg("deletion_ts") = "")
       .def("fetch", &NativeStore::fetch)
       .def("rv", &NativeStore::rv)
+      .def("peek", &NativeStore::peek)
       .def("contains", &NativeStore::contains)
-      .def("remove", &NativeStore::remove)
+      .def("remove", &NativeStore::remove, py::arg("kind"), py::arg("ns"),
+           py::arg("name"), py::arg("event_rv") = std::nullopt)
       .def("list_blobs", &NativeStore::list_blobs, py::arg("kind"),
-           py::arg("ns") = std::nullopt,
-           py::arg("selector") = std::vector<std::pair<std::string, std::string>>())
+           py::arg("ns") = std::nullopt, py::arg("selector") = LabelList())
       .def("list_views", &NativeStore::list_views, py::arg("ns") = std::nullopt,
-           py::arg("selector") = std::vector<std::pair<std::string, std::string>>())
+           py::arg("selector") = LabelList())
       .def("dependents", &NativeStore::dependents)
       .def("drop_owner", &NativeStore::drop_owner)
       .def("count", &NativeStore::count)
-      .def("total_bytes", &NativeStore::total_bytes);
+      .def("total_bytes", &NativeStore::total_bytes)
+      .def("history_since", &NativeStore::history_since, py::arg("rv"),
+           py::arg("kinds") = std::nullopt)
+      .def("history_reset", &NativeStore::history_reset, py::arg("base"),
+           py::arg("capacity") = 0)
+      .def("history_rvs", &NativeStore::history_rvs)
+      .def("stats", &NativeStore::stats);
 }

@@ -1,14 +1,21 @@
 """NativeBackend — the storage Backend over the C++ engine
-(kuberay_amd/_native/engine.cpp).
+(kuberay_amd/_native/engine.cpp + store_core.hpp).
 
-Objects are serialized once per write (compact JSON, CPython's C encoder)
-and live in the C++ heap; reads parse on demand; the reconcile hot loop
-reads precomputed pod views without touching the blob at all.
+The engine owns the encoding: a write hands it the dict tree and it encodes,
+indexes, computes the pod view and records the watch-history entry in one
+call; a status write re-encodes metadata + status only. Objects live in the
+C++ heap as shared JSON sections; reads parse on demand; the reconcile hot
+loop reads precomputed pod views without touching any JSON at all.
+
+Trees the native encoder declines (tuples, subclasses, non-str keys, big
+ints, NaN/Inf, lone surrogates, very deep nesting) take the json.dumps +
+put(blob) path and behave exactly as they always did.
 """
 from __future__ import annotations
 
 import json
-from typing import Any, Dict, List, Optional
+import os
+from typing import Any, Dict, List, Optional, Tuple
 
 from .._native import engine  # raises ImportError if not built
 from .store import Key, PodView
@@ -45,24 +52,57 @@ def _view_of(obj: Dict[str, Any]):
 class NativeBackend:
     name = "native-cpp"
 
-    def __init__(self) -> None:
-        self._store = engine.NativeStore()
+    # Measurement switches: with either off, that write takes the slower
+    # path it replaced (json.dumps + blob put / full re-encode), so the gain
+    # of each part can be told apart. Results are the same either way.
+    native_encode = os.environ.get("KUBERAY_STORE_NATIVE_ENCODE", "1") != "0"
+    status_splice = os.environ.get("KUBERAY_STORE_STATUS_SPLICE", "1") != "0"
+
+    def __init__(self, history_limit: int = 1024) -> None:
+        self._store = engine.NativeStore(history_limit)
         # kind -> live-object count; NativeStore has no kind enumeration,
         # and the HTTP facade needs one for dynamic (CRD) path routing
         self._kind_counts: Dict[str, int] = {}
 
-    def put(self, key: Key, obj: Dict[str, Any]) -> None:
+    def put(self, key: Key, obj: Dict[str, Any],
+            event_type: Optional[str] = None) -> None:
+        """Store ``obj``; with ``event_type`` the watch-history entry is
+        recorded in the same native call."""
         kind, ns, name = key
-        if not self._store.contains(kind, ns, name):
+        is_new = (self._store.put_object(kind, ns, name, obj, event_type)
+                  if self.native_encode else None)
+        if is_new is None:
+            is_new = self._put_blob(key, obj, event_type)
+        if is_new:
             self._kind_counts[kind] = self._kind_counts.get(kind, 0) + 1
+
+    def _put_blob(self, key: Key, obj: Dict[str, Any],
+                  event_type: Optional[str]) -> bool:
+        """The path for trees the native encoder declines: CPython's encoder
+        produces the blob, python the index fields."""
+        kind, ns, name = key
         meta = obj.get("metadata", {})
         labels = list((meta.get("labels") or {}).items())
         owners = [ref.get("uid") for ref in meta.get("ownerReferences") or []
                   if ref.get("uid")]
         view = _view_of(obj) if kind == "Pod" else None
         blob = _dumps(obj, separators=(",", ":"))
-        self._store.put(kind, ns, name, blob, meta.get("resourceVersion", ""),
-                        labels, owners, view)
+        uid = meta.get("uid")
+        deletion_ts = meta.get("deletionTimestamp") or ""
+        if not isinstance(deletion_ts, str):
+            deletion_ts = "set"  # only its truth is read back (peek)
+        return self._store.put(
+            kind, ns, name, blob, meta.get("resourceVersion", ""), labels,
+            owners, view, event_type, uid if isinstance(uid, str) else "",
+            bool(meta.get("finalizers")), deletion_ts)
+
+    def put_status(self, key: Key, obj: Dict[str, Any],
+                   event_type: Optional[str] = None) -> None:
+        """Status-subresource write: ``obj`` is the stored object with a new
+        status and resourceVersion, so only those two sections are encoded."""
+        if not self.status_splice or self._store.put_status(
+                key[0], key[1], key[2], obj, event_type) is None:
+            self.put(key, obj, event_type)
 
     def fetch(self, key: Key) -> Optional[Dict[str, Any]]:
         blob = self._store.fetch(*key)
@@ -71,18 +111,27 @@ class NativeBackend:
     def rv(self, key: Key) -> Optional[str]:
         return self._store.rv(*key)
 
+    def peek(self, key: Key) -> Optional[Tuple[str, str, bool, str]]:
+        """(resourceVersion, uid, has finalizers, deletionTimestamp) of the
+        stored object without touching its JSON; None when missing."""
+        return self._store.peek(*key)
+
     def contains(self, key: Key) -> bool:
         return self._store.contains(*key)
 
-    def remove(self, key: Key) -> Optional[Dict[str, Any]]:
-        blob = self._store.remove(*key)
-        if blob is not None:
-            n = self._kind_counts.get(key[0], 0) - 1
-            if n > 0:
-                self._kind_counts[key[0]] = n
-            else:
-                self._kind_counts.pop(key[0], None)
-        return _loads(blob) if blob is not None else None
+    def remove(self, key: Key,
+               event_rv: Optional[int] = None) -> Optional[Dict[str, Any]]:
+        """Remove and return the object; with ``event_rv`` the DELETED
+        history entry (carrying that rv) is recorded in the same call."""
+        blob = self._store.remove(key[0], key[1], key[2], event_rv)
+        if blob is None:
+            return None
+        n = self._kind_counts.get(key[0], 0) - 1
+        if n > 0:
+            self._kind_counts[key[0]] = n
+        else:
+            self._kind_counts.pop(key[0], None)
+        return _loads(blob)
 
     def list(self, kind: str, namespace: Optional[str],
              selector: Optional[Dict[str, str]]) -> List[Dict[str, Any]]:
@@ -115,3 +164,29 @@ class NativeBackend:
 
     def kinds(self) -> List[str]:
         return list(self._kind_counts)
+
+    # -- watch history (kept in the engine, in strict rv order) ----------
+    def history_since(self, rv: int, kinds: Optional[set] = None):
+        """[(event type, object)] with resourceVersion > rv, oldest first,
+        decoded on demand; None when rv predates the retained window."""
+        rows = self._store.history_since(rv, kinds)
+        if rows is None:
+            return None
+        out = []
+        for etype, blob, rv_override in rows:
+            obj = _loads(blob)
+            if rv_override is not None:
+                # a delete is its own revision; the sections still carry
+                # the object's last one
+                obj["metadata"]["resourceVersion"] = str(rv_override)
+            out.append((etype, obj))
+        return out
+
+    def history_reset(self, base: int, capacity: int = 0) -> None:
+        self._store.history_reset(base, capacity)
+
+    def history_rvs(self) -> List[int]:
+        return self._store.history_rvs()
+
+    def stats(self) -> Dict[str, int]:
+        return self._store.stats()

@@ -51,11 +51,9 @@ def load_snapshot(server: InMemoryApiServer, path: str) -> int:
         first = f.readline()
         meta = json.loads(first).get("__meta__", {}) if first.strip() else {}
         with server._lock:
-            server._rv = int(meta.get("resourceVersion", 0))
             # events before the restore point are unreplayable: watchers
             # resuming below this must 410 + re-list
-            server._history_base = server._rv
-            server._event_history.clear()
+            server.reset_history(int(meta.get("resourceVersion", 0)))
             for line in f:
                 line = line.strip()
                 if not line:

@@ -265,6 +265,16 @@ class InMemoryApiServer:
         # raised on snapshot restore (pre-restart events are gone — clients
         # below it must get 410 and re-list, never a silent gap)
         self._history_base: int = 0
+        # optional backend fast paths (the native engine has them): the
+        # backend records the watch history itself, in the same call as the
+        # write and from the bytes it stores anyway, splices status writes
+        # and answers delete's questions without parsing. Any backend
+        # without them gets the plain put/fetch/remove protocol and the
+        # python history above.
+        self._fast = all(hasattr(self._backend, n) for n in (
+            "put_status", "peek", "history_since", "history_reset"))
+        if self._fast:
+            self._backend.history_reset(0, self.EVENT_HISTORY_LIMIT)
 
     @property
     def backend_name(self) -> str:
@@ -275,23 +285,47 @@ class InMemoryApiServer:
         self._rv += 1
         return str(self._rv)
 
+    def _put(self, key: Key, obj: Dict[str, Any], event_type: str,
+             status_only: bool = False) -> None:
+        """Backend write (lock held). On the fast path the history entry for
+        ``event_type`` is recorded by the same call."""
+        if not self._fast:
+            self._backend.put(key, obj)
+        elif status_only:
+            self._backend.put_status(key, obj, event_type)
+        else:
+            self._backend.put(key, obj, event_type)
+
     def _notify(self, event_type: str, obj: Dict[str, Any]) -> None:
-        try:
-            rv = int(obj.get("metadata", {}).get("resourceVersion") or self._rv)
-        except (TypeError, ValueError):
-            rv = self._rv
-        if event_type == "DELETED":
-            # real apiserver: a delete is itself a new revision
-            rv = self._rv
-        # history entries are stored SERIALIZED: one compact string instead
-        # of ~10² nested dicts per event keeps the 1024-entry window at
-        # ~1 MB instead of ~11 MB resident (replay decodes on demand)
-        import json as _json
-        self._event_history.append(
-            (rv, event_type, obj.get("kind", ""),
-             _json.dumps(obj, separators=(",", ":"))))
+        if not self._fast:
+            try:
+                rv = int(obj.get("metadata", {}).get("resourceVersion") or self._rv)
+            except (TypeError, ValueError):
+                rv = self._rv
+            if event_type == "DELETED":
+                # real apiserver: a delete is itself a new revision
+                rv = self._rv
+            # history entries are stored SERIALIZED: one compact string
+            # instead of ~10² nested dicts per event keeps the 1024-entry
+            # window at ~1 MB instead of ~11 MB resident (replay decodes on
+            # demand)
+            import json as _json
+            self._event_history.append(
+                (rv, event_type, obj.get("kind", ""),
+                 _json.dumps(obj, separators=(",", ":"))))
         for w in list(self._watchers):
             w.push(event_type, obj)
+
+    def reset_history(self, rv: int) -> None:
+        """Snapshot restore: continue from revision ``rv`` with an empty
+        watch history. Events before the restore point are unreplayable, so
+        watchers resuming below it must get 410 and re-list."""
+        with self._lock:
+            self._rv = rv
+            self._history_base = rv
+            self._event_history.clear()
+            if self._fast:
+                self._backend.history_reset(rv, self.EVENT_HISTORY_LIMIT)
 
     @property
     def current_rv(self) -> int:
@@ -305,6 +339,10 @@ class InMemoryApiServer:
         the watch must be answered with 410 Gone and the client re-lists
         (kube-apiserver 'too old resource version' semantics).
         """
+        if self._fast:
+            # the engine keeps the ring; blobs are decoded on demand and a
+            # DELETED entry gets the delete's own rv put back in
+            return self._backend.history_since(rv, kinds)
         import json as _json
         with self._lock:
             hist = self._event_history
@@ -341,7 +379,7 @@ class InMemoryApiServer:
             meta["resourceVersion"] = self._next_rv()
             meta["generation"] = 1
             meta["creationTimestamp"] = now_iso()
-            self._backend.put(key, obj)
+            self._put(key, obj, "ADDED")
         self._notify("ADDED", obj)
         return obj
 
@@ -383,118 +421,165 @@ class InMemoryApiServer:
             current = self._backend.fetch(key)
             if current is None:
                 raise NotFoundError(f"{key} not found")
-            meta = obj.setdefault("metadata", {})
-            rv = meta.get("resourceVersion")
-            cur_meta = current["metadata"]
-            if rv is not None and rv != cur_meta["resourceVersion"]:
-                raise ConflictError(
-                    f"{key}: resourceVersion mismatch {rv} != {cur_meta['resourceVersion']}")
-            if subresource == "status":
-                new_obj = current
-                new_obj["status"] = obj.get("status", {})
-            else:
-                new_obj = obj
-                if new_obj.get("spec") != current.get("spec"):
-                    new_obj["metadata"]["generation"] = cur_meta.get("generation", 1) + 1
-                else:
-                    new_obj["metadata"]["generation"] = cur_meta.get("generation", 1)
-                new_obj["status"] = current.get("status", {})
-            new_obj["metadata"]["uid"] = cur_meta["uid"]
-            new_obj["metadata"]["creationTimestamp"] = cur_meta["creationTimestamp"]
-            if cur_meta.get("deletionTimestamp"):
-                new_obj["metadata"]["deletionTimestamp"] = cur_meta["deletionTimestamp"]
-            new_obj["metadata"]["resourceVersion"] = self._next_rv()
-            self._backend.put(key, new_obj)
-            finalizers_gone = (
-                cur_meta.get("deletionTimestamp")
-                and not new_obj["metadata"].get("finalizers"))
+            new_obj, finalizers_gone = self._apply_update(
+                key, obj, current, subresource)
         self._notify("MODIFIED", new_obj)
         if finalizers_gone:
             self._finalize_delete(key)
         return new_obj
 
+    def _apply_update(self, key: Key, obj: Dict[str, Any],
+                      current: Dict[str, Any], subresource: Optional[str]):
+        """The update rules, given the stored object already fetched (lock
+        held; both trees are the caller's to edit). Writes the result and
+        returns ``(stored object, finalizers gone while deleting)``; the
+        caller notifies and finishes the delete outside the lock."""
+        meta = obj.setdefault("metadata", {})
+        rv = meta.get("resourceVersion")
+        cur_meta = current["metadata"]
+        if rv is not None and rv != cur_meta["resourceVersion"]:
+            raise ConflictError(
+                f"{key}: resourceVersion mismatch {rv} != {cur_meta['resourceVersion']}")
+        if subresource == "status":
+            # the status subresource takes everything but status from the
+            # stored object
+            new_obj = current
+            new_obj["status"] = obj.get("status", {})
+        else:
+            new_obj = obj
+            if new_obj.get("spec") != current.get("spec"):
+                new_obj["metadata"]["generation"] = cur_meta.get("generation", 1) + 1
+            else:
+                new_obj["metadata"]["generation"] = cur_meta.get("generation", 1)
+            new_obj["status"] = current.get("status", {})
+        new_obj["metadata"]["uid"] = cur_meta["uid"]
+        new_obj["metadata"]["creationTimestamp"] = cur_meta["creationTimestamp"]
+        if cur_meta.get("deletionTimestamp"):
+            new_obj["metadata"]["deletionTimestamp"] = cur_meta["deletionTimestamp"]
+        new_obj["metadata"]["resourceVersion"] = self._next_rv()
+        self._put(key, new_obj, "MODIFIED",
+                  status_only=subresource == "status")
+        finalizers_gone = (
+            cur_meta.get("deletionTimestamp")
+            and not new_obj["metadata"].get("finalizers"))
+        return new_obj, finalizers_gone
+
     def patch_merge(self, kind: str, namespace: str, name: str,
                     patch: Dict[str, Any], *, subresource: Optional[str] = None,
                     ) -> Dict[str, Any]:
-        """Strategic-merge-ish patch (recursive dict merge; lists replaced)."""
-        with self._lock:
-            merged = self._backend.fetch((kind, namespace, name))
-            if merged is None:
-                raise NotFoundError(f"{kind} {namespace}/{name} not found")
-
-            def merge(dst, src):
-                for k, v in src.items():
-                    if isinstance(v, dict):
-                        # RFC 7386: patch objects merge into the existing
-                        # value or {} — nested nulls delete, never
-                        # materialize (keeps merge patch idempotent)
-                        node = dst.get(k)
-                        if not isinstance(node, dict):
-                            node = dst[k] = {}
-                        merge(node, v)
-                    elif v is None:
-                        dst.pop(k, None)
-                    else:
-                        dst[k] = jsoncopy(v)
-
-            target = merged if subresource is None else merged.setdefault(
-                "status", {})
-            if subresource == "status":
-                merge(target, patch.get("status", patch))
-            else:
-                merge(merged, patch)
-        return self.update(merged, subresource=subresource)
-
-    def mutate_status(self, kind: str, namespace: str, name: str,
-                      fn) -> Optional[Dict[str, Any]]:
-        """Single-fetch status mutation: ``fn(obj)`` edits ``obj['status']``
-        in place (or returns False to skip the write). One backend
-        fetch/parse instead of the try_get + patch_merge pair — the sim
-        kubelet's pod-start transition is hot enough at 2000-pod bursts for
-        the double parse to show up in profiles. Returns the stored object,
-        or None when skipped/missing."""
-        for attempt in (0, 1):
-            with self._lock:
-                obj = self._backend.fetch((kind, namespace, name))
-                if obj is None:
-                    return None
-                if fn(obj) is False:
-                    return None
-            try:
-                return self.update(obj, subresource="status")
-            except ConflictError:
-                if attempt:
-                    raise
-        return None  # unreachable; loop always returns or raises
-
-    def delete(self, kind: str, namespace: str, name: str) -> None:
+        """Strategic-merge-ish patch (recursive dict merge; lists replaced).
+        One fetch, one write, one lock hold."""
         key = (kind, namespace, name)
+
+        def merge(dst, src):
+            for k, v in src.items():
+                if isinstance(v, dict):
+                    # RFC 7386: patch objects merge into the existing
+                    # value or {} — nested nulls delete, never
+                    # materialize (keeps merge patch idempotent)
+                    node = dst.get(k)
+                    if not isinstance(node, dict):
+                        node = dst[k] = {}
+                    merge(node, v)
+                elif v is None:
+                    dst.pop(k, None)
+                else:
+                    dst[k] = jsoncopy(v)
+
         with self._lock:
             current = self._backend.fetch(key)
             if current is None:
                 raise NotFoundError(f"{kind} {namespace}/{name} not found")
-            if current["metadata"].get("finalizers"):
-                if current["metadata"].get("deletionTimestamp"):
+            if subresource == "status":
+                # only the status is taken from the patched tree
+                merged = current
+                merge(merged.setdefault("status", {}),
+                      patch.get("status", patch))
+            else:
+                # the update rules compare the patched tree with the stored
+                # one, so the patch goes onto a copy of the one parsed tree
+                merged = jsoncopy(current)
+                if subresource is not None:
+                    merged.setdefault("status", {})
+                merge(merged, patch)
+            if self._key_of(merged) != key:
+                # the patch renamed the object: update() addresses whatever
+                # the patched tree names
+                return self.update(merged, subresource=subresource,
+                                   assume_owned=True)
+            new_obj, finalizers_gone = self._apply_update(
+                key, merged, current, subresource)
+        self._notify("MODIFIED", new_obj)
+        if finalizers_gone:
+            self._finalize_delete(key)
+        return new_obj
+
+    def mutate_status(self, kind: str, namespace: str, name: str,
+                      fn) -> Optional[Dict[str, Any]]:
+        """Single-fetch status mutation: ``fn(obj)`` edits ``obj['status']``
+        in place (or returns False to skip the write). One backend fetch and
+        parse, one write, one lock hold — the sim kubelet's pod-start
+        transition is hot enough at 2000-pod bursts for anything more to
+        show up in profiles. ``fn`` runs under the store lock and must edit
+        nothing but the status. Returns the stored object, or None when
+        skipped/missing."""
+        key = (kind, namespace, name)
+        with self._lock:
+            obj = self._backend.fetch(key)
+            if obj is None:
+                return None
+            if fn(obj) is False:
+                return None
+            new_obj, finalizers_gone = self._apply_update(
+                key, obj, obj, "status")
+        self._notify("MODIFIED", new_obj)
+        if finalizers_gone:
+            self._finalize_delete(key)
+        return new_obj
+
+    def delete(self, kind: str, namespace: str, name: str) -> None:
+        key = (kind, namespace, name)
+        with self._lock:
+            if self._fast:
+                # decided from the fields the engine keeps beside the
+                # object; nothing is parsed unless the delete is blocked
+                peeked = self._backend.peek(key)
+                if peeked is None:
+                    raise NotFoundError(f"{kind} {namespace}/{name} not found")
+                _, _, has_finalizers, deletion_ts = peeked
+                if has_finalizers and deletion_ts:
                     return
+                current = self._backend.fetch(key) if has_finalizers else None
+            else:
+                current = self._backend.fetch(key)
+                if current is None:
+                    raise NotFoundError(f"{kind} {namespace}/{name} not found")
+                if not current["metadata"].get("finalizers"):
+                    current = None
+                elif current["metadata"].get("deletionTimestamp"):
+                    return
+            if current is not None:
                 current["metadata"]["deletionTimestamp"] = now_iso()
                 current["metadata"]["resourceVersion"] = self._next_rv()
-                self._backend.put(key, current)
-                out = current
-            else:
-                out = None
-        if out is not None:
-            self._notify("MODIFIED", out)
+                self._put(key, current, "MODIFIED")
+        if current is not None:
+            self._notify("MODIFIED", current)
             return
         self._finalize_delete(key)
 
     def _finalize_delete(self, key: Key) -> None:
         with self._lock:
-            current = self._backend.remove(key)
-            if current is None:
-                return
             # a delete is its own revision (real-apiserver semantics):
             # without a fresh rv, a watcher resuming from the object's last
             # rv would treat the DELETED event as already-seen and miss it
+            if self._fast:
+                # the engine records the DELETED entry from the sections it
+                # already holds; this parse is for the watchers
+                current = self._backend.remove(key, self._rv + 1)
+            else:
+                current = self._backend.remove(key)
+            if current is None:
+                return
             current["metadata"]["resourceVersion"] = self._next_rv()
             uid = current["metadata"]["uid"]
             dependents = self._backend.dependents(uid)
