@@ -2,7 +2,8 @@
 live next to the sources so it travels to GPU boxes with the repo snapshot).
 
 Extensions:
-  * gpuhealth  — HIP/gfx950 on-device health probes (gpuhealth.hip)
+  * gpuhealth  — HIP/gfx950 on-device health probes and burn-in
+                 (gpuhealth.hip over gpuhealth_ref.hpp)
   * engine     — C++ control-plane core: object cache + indices + native
                  JSON encoding (engine.cpp bindings over store_core.hpp)
 
@@ -41,7 +42,7 @@ def _needs_rebuild(src: Path, out: Path, *deps: Path) -> bool:
 def build_gpuhealth(force: bool = False) -> Path:
     src = HERE / "gpuhealth.hip"
     out = HERE / f"gpuhealth{_ext_suffix()}"
-    if not force and not _needs_rebuild(src, out):
+    if not force and not _needs_rebuild(src, out, HERE / "gpuhealth_ref.hpp"):
         return out
     cmd = [
         HIPCC, f"--offload-arch={GFX_ARCH}", "-O3", "-std=c++17",

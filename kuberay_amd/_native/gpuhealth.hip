@@ -4,17 +4,38 @@
 // (kuberay_amd/gpu/health.py, wired into pod readiness probes by
 // kuberay_amd/common/pod.py). The reference operator (kuberay) has no
 // GPU-level probing at all; on MI355X nodes a pod can be "Ready" while its
-// GPU is wedged (queue hang, HBM fallout, xGMI link down). These probes are
-// cheap (<50 ms) and catch that:
+// GPU is wedged (queue hang, HBM fallout, xGMI link down).
+//
+// Quick gate (readiness/liveness, <50 ms) — proves the device executes and
+// streams; it does not look at the data and cannot see silent corruption:
 //
 //   * mfma_smoke   — one wave per workgroup issues v_mfma_f32_16x16x32_bf16
 //                    with all-ones inputs; every D element must equal K=32.
-//                    Proves the matrix pipeline executes and returns.
+//                    Proves the matrix pipeline executes and returns. All-ones
+//                    data is blind to lane routing and to low operand bits.
 //   * hbm_stream   — float4 streaming copy sized ≫ L3 (256 MiB) across
 //                    ≫256 workgroups; host computes GB/s and compares
 //                    against a floor (healthy MI355X streams ≈6 TB/s; a
 //                    sick HBM stack or thermally-parked clock shows up as a
-//                    collapse by an order of magnitude).
+//                    collapse by an order of magnitude). The copied data is
+//                    never compared: bandwidth only.
+//
+// Burn-in level (opt-in startup probe, seconds) — verifies data:
+//
+//   * hbm_pattern  — fills up to a fraction of the free HBM (all chunks live
+//                    at once) with an index-hashed pattern, re-derives and
+//                    compares it, then repeats with the pattern inverted.
+//                    Reports mismatching words, flipped bits, the OR of the
+//                    differences (a stuck line is one bit) and the first bad
+//                    offset.
+//   * mfma_exact   — asymmetric hashed operands whose products are exact in
+//                    fp32, through bf16, f16, OCP fp8 and block-scaled MXFP4
+//                    MFMA, with a C input; D is checked element by element
+//                    against integer dot products computed off the matrix
+//                    pipeline. Any lane-routing or operand-bit fault shows.
+//
+// What must agree between host and device (pattern, generators, encoders,
+// reference) is in gpuhealth_ref.hpp.
 //
 // Build: hipcc --offload-arch=gfx950 (see kuberay_amd/_native/build.py).
 // Wavefront width is 64 on CDNA4 — all wave math below hard-codes 64.
@@ -24,10 +45,13 @@
 #include <pybind11/pybind11.h>
 #include <pybind11/stl.h>
 
+#include <algorithm>
 #include <cstdint>
 #include <stdexcept>
 #include <string>
 #include <vector>
+
+#include "gpuhealth_ref.hpp"
 
 namespace py = pybind11;
 
@@ -133,6 +157,396 @@ static double run_hbm_stream(size_t bytes, int iters) {
 }
 
 // ---------------------------------------------------------------------------
+// Burn-in, part 1: HBM pattern sweep (fill, then re-derive and compare)
+// ---------------------------------------------------------------------------
+struct PatternStats {
+  unsigned long long mismatched_words;
+  unsigned long long flipped_bits;
+  unsigned long long first_bad_word;  // global word index, ~0 when clean
+  unsigned int bad_bit_mask;          // OR of every XOR difference
+};
+
+static constexpr unsigned long long kNoBadWord = ~0ull;
+
+// n_vec 16-byte vectors; vector i holds words base_word + 4i .. + 4i+3
+__global__ void hbm_pattern_fill(uint4* __restrict__ buf, uint64_t n_vec,
+                                 uint64_t base_word, uint32_t seed,
+                                 uint32_t invert_mask) {
+  uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+  for (; i < n_vec; i += stride) {
+    const uint64_t w = base_word + 4 * i;
+    uint4 v;
+    v.x = gh::pattern_word(seed, w) ^ invert_mask;
+    v.y = gh::pattern_word(seed, w + 1) ^ invert_mask;
+    v.z = gh::pattern_word(seed, w + 2) ^ invert_mask;
+    v.w = gh::pattern_word(seed, w + 3) ^ invert_mask;
+    buf[i] = v;
+  }
+}
+
+__device__ inline unsigned long long wave_min_u64(unsigned long long v) {
+  for (int off = 32; off > 0; off >>= 1) {
+    const unsigned long long o = __shfl_xor(v, off, 64);
+    v = o < v ? o : v;
+  }
+  return v;
+}
+__device__ inline unsigned long long wave_sum_u64(unsigned long long v) {
+  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+  return v;
+}
+__device__ inline unsigned int wave_or_u32(unsigned int v) {
+  for (int off = 32; off > 0; off >>= 1) v |= __shfl_xor(v, off, 64);
+  return v;
+}
+
+__global__ void hbm_pattern_verify(const uint4* __restrict__ buf, uint64_t n_vec,
+                                   uint64_t base_word, uint32_t seed,
+                                   uint32_t invert_mask,
+                                   PatternStats* __restrict__ stats) {
+  unsigned long long bad = 0, bits = 0, first = kNoBadWord;
+  unsigned int mask = 0;
+  uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+  for (; i < n_vec; i += stride) {
+    const uint64_t w = base_word + 4 * i;
+    const uint4 v = buf[i];
+    const uint32_t got[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const uint32_t x = got[j] ^ gh::pattern_word(seed, w + j) ^ invert_mask;
+      if (x != 0) {
+        ++bad;
+        bits += __popc(x);
+        mask |= x;
+        if (w + j < first) first = w + j;
+      }
+    }
+  }
+  // per-lane partials -> wave reduction -> one atomic per wave, and only for a
+  // wave that saw a mismatch: a clean sweep issues no atomics at all
+  if (__ballot(bad != 0) == 0) return;
+  bad = wave_sum_u64(bad);
+  bits = wave_sum_u64(bits);
+  first = wave_min_u64(first);
+  mask = wave_or_u32(mask);
+  if ((threadIdx.x & 63) == 0) {
+    atomicAdd(&stats->mismatched_words, bad);
+    atomicAdd(&stats->flipped_bits, bits);
+    atomicMin(&stats->first_bad_word, first);
+    atomicOr(&stats->bad_bit_mask, mask);
+  }
+}
+
+// Frees every device allocation and event it was handed, on every path out.
+struct DeviceScope {
+  std::vector<void*> ptrs;
+  std::vector<hipEvent_t> events;
+  ~DeviceScope() {
+    for (hipEvent_t e : events) (void)hipEventDestroy(e);
+    for (void* p : ptrs) (void)hipFree(p);
+  }
+  void* alloc(size_t bytes) {
+    void* p = nullptr;
+    HIP_CHECK(hipMalloc(&p, bytes));
+    ptrs.push_back(p);
+    return p;
+  }
+  hipEvent_t event() {
+    hipEvent_t e;
+    HIP_CHECK(hipEventCreate(&e));
+    events.push_back(e);
+    return e;
+  }
+};
+
+static int pattern_blocks(uint64_t n_vec) {
+  // ≫256 workgroups to fill 8 XCDs, as the stream kernel; fewer for tiny runs
+  const uint64_t want = (n_vec + 255) / 256;
+  return (int)(want < 4096 ? (want ? want : 1) : 4096);
+}
+
+struct PatternResult {
+  uint64_t bytes_checked = 0;
+  int chunks = 0;
+  PatternStats stats{0, 0, kNoBadWord, 0};
+  double gb_s = 0.0;
+};
+
+// target_bytes > 0: sweep exactly that much; else fraction x free memory.
+// corrupt_word >= 0: the host flips corrupt_bit of that (global) word between
+// the first fill and its verify.
+static PatternResult run_hbm_pattern(uint64_t target_bytes, double fraction,
+                                     uint32_t seed, int passes,
+                                     uint64_t max_chunk_bytes,
+                                     int64_t corrupt_word, int corrupt_bit) {
+  if (target_bytes == 0) {
+    if (!(fraction > 0.0) || fraction > 1.0)
+      throw py::value_error("fraction must be in (0, 1] when no size is given");
+    size_t free_b = 0, total_b = 0;
+    HIP_CHECK(hipMemGetInfo(&free_b, &total_b));
+    target_bytes = (uint64_t)((double)free_b * fraction);
+    target_bytes &= ~(uint64_t)15;
+    if (target_bytes == 0) throw std::runtime_error("no free device memory to sweep");
+  }
+  if (target_bytes % 16 != 0) throw py::value_error("size must be a multiple of 16 bytes");
+  if (max_chunk_bytes == 0 || max_chunk_bytes % 16 != 0)
+    throw py::value_error("chunk size must be a positive multiple of 16 bytes");
+  if (passes < 1) throw py::value_error("passes must be >= 1");
+  if (corrupt_bit < 0 || corrupt_bit > 31) throw py::value_error("corrupt_bit must be in [0, 31]");
+  if (corrupt_word < -1 || (corrupt_word >= 0 && (uint64_t)corrupt_word >= target_bytes / 4))
+    throw py::value_error("corrupt_word is outside the swept range");
+
+  struct Chunk { uint4* ptr; uint64_t bytes; uint64_t base_word; };
+  DeviceScope scope;
+  std::vector<Chunk> chunks;
+  uint64_t covered = 0;
+  // all chunks stay live together: free + re-allocate would hand back the
+  // same pages and test them twice
+  while (covered < target_bytes) {
+    const uint64_t want = std::min(max_chunk_bytes, target_bytes - covered);
+    void* p = nullptr;
+    if (hipMalloc(&p, want) != hipSuccess) {
+      (void)hipGetLastError();  // out of memory ends the allocation phase
+      break;
+    }
+    scope.ptrs.push_back(p);
+    chunks.push_back({(uint4*)p, want, covered / 4});
+    covered += want;
+  }
+  if (chunks.empty()) throw std::runtime_error("could not allocate any device memory to sweep");
+  if (corrupt_word >= 0 && (uint64_t)corrupt_word >= covered / 4)
+    throw py::value_error("corrupt_word is outside the memory that could be allocated");
+
+  PatternStats* d_stats = (PatternStats*)scope.alloc(sizeof(PatternStats));
+  PatternResult res;
+  HIP_CHECK(hipMemcpy(d_stats, &res.stats, sizeof(PatternStats), hipMemcpyHostToDevice));
+
+  hipEvent_t t0 = scope.event(), t1 = scope.event();
+  HIP_CHECK(hipEventRecord(t0, 0));
+  for (int pass = 0; pass < passes; ++pass) {
+    // moving inversion: every bit is driven to 0 and to 1 and read back
+    for (int phase = 0; phase < 2; ++phase) {
+      const uint32_t inv = phase ? 0xFFFFFFFFu : 0u;
+      for (const Chunk& c : chunks) {
+        const uint64_t n_vec = c.bytes / 16;
+        hipLaunchKernelGGL(hbm_pattern_fill, dim3(pattern_blocks(n_vec)), dim3(256),
+                           0, 0, c.ptr, n_vec, c.base_word, seed, inv);
+      }
+      HIP_CHECK(hipGetLastError());
+      if (corrupt_word >= 0 && pass == 0 && phase == 0) {
+        for (const Chunk& c : chunks) {
+          const uint64_t w = (uint64_t)corrupt_word;
+          if (w < c.base_word || w >= c.base_word + c.bytes / 4) continue;
+          uint32_t* addr = (uint32_t*)c.ptr + (w - c.base_word);
+          uint32_t word = 0;
+          HIP_CHECK(hipMemcpy(&word, addr, 4, hipMemcpyDeviceToHost));
+          word ^= 1u << corrupt_bit;
+          HIP_CHECK(hipMemcpy(addr, &word, 4, hipMemcpyHostToDevice));
+        }
+      }
+      for (const Chunk& c : chunks) {
+        const uint64_t n_vec = c.bytes / 16;
+        hipLaunchKernelGGL(hbm_pattern_verify, dim3(pattern_blocks(n_vec)), dim3(256),
+                           0, 0, c.ptr, n_vec, c.base_word, seed, inv, d_stats);
+      }
+      HIP_CHECK(hipGetLastError());
+    }
+  }
+  HIP_CHECK(hipEventRecord(t1, 0));
+  HIP_CHECK(hipEventSynchronize(t1));
+  float ms = 0.f;
+  HIP_CHECK(hipEventElapsedTime(&ms, t0, t1));
+  HIP_CHECK(hipMemcpy(&res.stats, d_stats, sizeof(PatternStats), hipMemcpyDeviceToHost));
+  res.bytes_checked = covered;
+  res.chunks = (int)chunks.size();
+  // per pass: two fills (write) and two verifies (read) of every byte
+  res.gb_s = ms > 0.f ? 4.0 * (double)covered * passes / (ms * 1e-3) / 1e9 : 0.0;
+  return res;
+}
+
+// ---------------------------------------------------------------------------
+// Burn-in, part 2: exact, layout-sensitive MFMA verification
+//
+// Operand lane maps (lane l, i = l & 15, g = l >> 4):
+//   bf16 / f16 16x16x32 : fragment element j (0..7)  = A[i][8g + j], B[8g + j][i]
+//   fp8 16x16x32        : byte j (0..7) of the 64-bit operand, same k = 8g + j
+//   f8f6f4 16x16x128 FP4: nibble j (0..31) of the first 4 operand VGPRs is
+//                         k = 32g + j, the even element in the low nibble; the
+//                         lane's scale byte is the E8M0 of (row/col i, block g)
+//   C/D (all paths)     : register r = D[4g + r][i]
+// The maps are proven on the device by tests/test_gpu_burn_in.py: with
+// asymmetric hashed data D equals A·B + C exactly only if all are right.
+// ---------------------------------------------------------------------------
+typedef __attribute__((ext_vector_type(8))) _Float16 frag_f16_t;
+typedef __attribute__((ext_vector_type(8))) int frag_i32x8_t;
+
+template <int DT>
+__device__ inline frag_cd_t mfma_exact_tile(uint32_t seed, uint32_t wg, int lane,
+                                            frag_cd_t acc) {
+  const uint32_t i = lane & 15, g = lane >> 4;
+  if constexpr (DT == gh::BF16) {
+    frag_ab_t a, b;
+    for (uint32_t j = 0; j < 8; ++j) {
+      a[j] = __builtin_bit_cast(__bf16, gh::f32_to_bf16(
+          (float)gh::gen_int(seed, wg, DT, gh::GEN_A, i, 8 * g + j)));
+      b[j] = __builtin_bit_cast(__bf16, gh::f32_to_bf16(
+          (float)gh::gen_int(seed, wg, DT, gh::GEN_B, i, 8 * g + j)));
+    }
+    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, acc, 0, 0, 0);
+  } else if constexpr (DT == gh::F16) {
+    frag_f16_t a, b;
+    for (uint32_t j = 0; j < 8; ++j) {
+      a[j] = __builtin_bit_cast(_Float16, gh::f32_to_f16(
+          (float)gh::gen_int(seed, wg, DT, gh::GEN_A, i, 8 * g + j)));
+      b[j] = __builtin_bit_cast(_Float16, gh::f32_to_f16(
+          (float)gh::gen_int(seed, wg, DT, gh::GEN_B, i, 8 * g + j)));
+    }
+    return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, acc, 0, 0, 0);
+  } else if constexpr (DT == gh::FP8) {
+    uint64_t a = 0, b = 0;
+    for (uint32_t j = 0; j < 8; ++j) {
+      a |= (uint64_t)gh::f32_to_e4m3(
+               (float)gh::gen_int(seed, wg, DT, gh::GEN_A, i, 8 * g + j)) << (8 * j);
+      b |= (uint64_t)gh::f32_to_e4m3(
+               (float)gh::gen_int(seed, wg, DT, gh::GEN_B, i, 8 * g + j)) << (8 * j);
+    }
+    return __builtin_amdgcn_mfma_f32_16x16x32_fp8_fp8((long)a, (long)b, acc, 0, 0, 0);
+  } else {
+    frag_i32x8_t a = {0, 0, 0, 0, 0, 0, 0, 0}, b = {0, 0, 0, 0, 0, 0, 0, 0};
+    for (uint32_t v = 0; v < 4; ++v) {
+      uint32_t wa = 0, wb = 0;
+      for (uint32_t n = 0; n < 8; ++n) {
+        const uint32_t k = 32 * g + 8 * v + n;
+        wa |= gh::gen_fp4(seed, wg, gh::GEN_A, i, k) << (4 * n);
+        wb |= gh::gen_fp4(seed, wg, gh::GEN_B, i, k) << (4 * n);
+      }
+      a[v] = (int)wa;
+      b[v] = (int)wb;
+    }
+    const int sa = (int)gh::gen_scale(seed, wg, gh::GEN_SA, i, g);
+    const int sb = (int)gh::gen_scale(seed, wg, gh::GEN_SB, i, g);
+    // cbsz=4 / blgp=4: FP4 A and B; opsel 0: scale is byte 0 of the operand
+    return __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(a, b, acc, 4, 4, 0, sa, 0, sb);
+  }
+}
+
+// one wave per workgroup; D tiles are row-major, tile wg at out + 256 * wg
+template <int DT>
+__global__ void mfma_exact_kernel(float* __restrict__ out, uint32_t seed,
+                                  uint32_t wg_base) {
+  const int lane = threadIdx.x & 63;
+  const uint32_t wg = wg_base + blockIdx.x;
+  const uint32_t col = lane & 15, row0 = 4 * (lane >> 4);
+  frag_cd_t acc;
+  for (uint32_t r = 0; r < 4; ++r) acc[r] = (float)gh::gen_c(seed, wg, DT, row0 + r, col);
+  acc = mfma_exact_tile<DT>(seed, wg, lane, acc);
+  float* tile = out + (size_t)blockIdx.x * 256;
+  for (uint32_t r = 0; r < 4; ++r) tile[(row0 + r) * 16 + col] = acc[r];
+}
+
+struct MfmaStats {
+  unsigned long long mismatches;
+  unsigned long long first_bad;  // flat element index, ~0 when clean
+};
+
+// Checks D without the matrix pipeline: integer dot products over the same
+// generators, four outputs per lane.
+__global__ void mfma_check_kernel(const float* __restrict__ d, int dtype,
+                                  uint32_t seed, uint32_t wg_base,
+                                  MfmaStats* __restrict__ stats) {
+  const int lane = threadIdx.x & 63;
+  const uint32_t wg = wg_base + blockIdx.x;
+  const uint32_t col = lane & 15, row0 = 4 * (lane >> 4);
+  unsigned long long bad = 0, first = kNoBadWord;
+  for (uint32_t r = 0; r < 4; ++r) {
+    const size_t idx = (size_t)blockIdx.x * 256 + (row0 + r) * 16 + col;
+    const float expected = gh::reference_element(dtype, seed, wg, row0 + r, col);
+    if (!(d[idx] == expected)) {
+      ++bad;
+      if (idx < first) first = idx;
+    }
+  }
+  if (__ballot(bad != 0) == 0) return;
+  bad = wave_sum_u64(bad);
+  first = wave_min_u64(first);
+  if (lane == 0) {
+    atomicAdd(&stats->mismatches, bad);
+    atomicMin(&stats->first_bad, first);
+  }
+}
+
+static void launch_mfma_exact(int dtype, float* d_out, int workgroups,
+                              uint32_t seed, uint32_t wg_base) {
+  const dim3 grid(workgroups), block(64);
+  switch (dtype) {
+    case gh::BF16:
+      hipLaunchKernelGGL(mfma_exact_kernel<gh::BF16>, grid, block, 0, 0, d_out, seed, wg_base);
+      break;
+    case gh::F16:
+      hipLaunchKernelGGL(mfma_exact_kernel<gh::F16>, grid, block, 0, 0, d_out, seed, wg_base);
+      break;
+    case gh::FP8:
+      hipLaunchKernelGGL(mfma_exact_kernel<gh::FP8>, grid, block, 0, 0, d_out, seed, wg_base);
+      break;
+    default:
+      hipLaunchKernelGGL(mfma_exact_kernel<gh::MXFP4>, grid, block, 0, 0, d_out, seed, wg_base);
+      break;
+  }
+  HIP_CHECK(hipGetLastError());
+}
+
+struct MfmaResult {
+  int tiles = 0;
+  uint64_t mismatches = 0;
+  int64_t first_bad = -1;  // flat element index
+  float got = 0.f, expected = 0.f;
+};
+
+// corrupt_element >= 0: the host flips one mantissa bit of that element of D
+// ((workgroup * 16 + row) * 16 + col) between the MFMA pass and the check.
+static MfmaResult run_mfma_verify(int dtype, int workgroups, uint32_t seed,
+                                  int64_t corrupt_element) {
+  if (workgroups < 1 || workgroups > (1 << 20))
+    throw py::value_error("workgroups must be in [1, 2^20]");
+  const size_t n = (size_t)workgroups * 256;
+  if (corrupt_element < -1 || (corrupt_element >= 0 && (uint64_t)corrupt_element >= n))
+    throw py::value_error("corrupt_element is outside the output buffer");
+
+  DeviceScope scope;
+  float* d_out = (float*)scope.alloc(n * sizeof(float));
+  MfmaStats* d_stats = (MfmaStats*)scope.alloc(sizeof(MfmaStats));
+  MfmaStats st{0, kNoBadWord};
+  HIP_CHECK(hipMemcpy(d_stats, &st, sizeof(st), hipMemcpyHostToDevice));
+
+  launch_mfma_exact(dtype, d_out, workgroups, seed, 0);
+  if (corrupt_element >= 0) {
+    uint32_t word = 0;
+    HIP_CHECK(hipMemcpy(&word, d_out + corrupt_element, 4, hipMemcpyDeviceToHost));
+    word ^= 1u << 20;
+    HIP_CHECK(hipMemcpy(d_out + corrupt_element, &word, 4, hipMemcpyHostToDevice));
+  }
+  hipLaunchKernelGGL(mfma_check_kernel, dim3(workgroups), dim3(64), 0, 0,
+                     d_out, dtype, seed, 0u, d_stats);
+  HIP_CHECK(hipGetLastError());
+  HIP_CHECK(hipDeviceSynchronize());
+  HIP_CHECK(hipMemcpy(&st, d_stats, sizeof(st), hipMemcpyDeviceToHost));
+
+  MfmaResult res;
+  res.tiles = workgroups;
+  res.mismatches = st.mismatches;
+  if (st.mismatches != 0 && st.first_bad < n) {
+    res.first_bad = (int64_t)st.first_bad;
+    HIP_CHECK(hipMemcpy(&res.got, d_out + st.first_bad, 4, hipMemcpyDeviceToHost));
+    res.expected = gh::reference_element(dtype, seed, (uint32_t)(st.first_bad / 256),
+                                         (uint32_t)(st.first_bad / 16 % 16),
+                                         (uint32_t)(st.first_bad % 16));
+  }
+  return res;
+}
+
+// ---------------------------------------------------------------------------
 // host API
 // ---------------------------------------------------------------------------
 static int device_count() {
@@ -182,8 +596,143 @@ static py::dict health_check(int device, double hbm_floor_gb_s, bool quick) {
   return result;
 }
 
+// -- burn-in bindings --------------------------------------------------------
+static int parse_dtype(const std::string& s) {
+  if (s == "bf16") return gh::BF16;
+  if (s == "f16") return gh::F16;
+  if (s == "fp8") return gh::FP8;
+  if (s == "mxfp4") return gh::MXFP4;
+  throw py::value_error("dtype must be one of bf16, f16, fp8, mxfp4 (got '" + s + "')");
+}
+
+static py::dict pattern_dict(const PatternResult& r) {
+  py::dict d;
+  d["bytes_checked"] = r.bytes_checked;
+  d["chunks"] = r.chunks;
+  d["mismatched_words"] = r.stats.mismatched_words;
+  d["flipped_bits"] = r.stats.flipped_bits;
+  d["bad_bit_mask"] = r.stats.bad_bit_mask;
+  d["first_bad_offset"] = r.stats.first_bad_word == kNoBadWord
+                              ? (int64_t)-1 : (int64_t)(4 * r.stats.first_bad_word);
+  d["gb_s"] = r.gb_s;
+  return d;
+}
+
+static py::dict hbm_pattern_check(int device, double mib, double fraction,
+                                  uint32_t seed, int64_t corrupt_word,
+                                  int corrupt_bit, uint64_t bytes,
+                                  uint64_t max_chunk_mib, int passes) {
+  if (bytes == 0 && fraction == 0.0) {
+    if (!(mib > 0.0)) throw py::value_error("mib must be positive");
+    bytes = (uint64_t)(mib * 1048576.0) & ~(uint64_t)15;
+  }
+  if (max_chunk_mib == 0 || max_chunk_mib > 16384)
+    throw py::value_error("max_chunk_mib must be in [1, 16384]");
+  HIP_CHECK(hipSetDevice(device));
+  return pattern_dict(run_hbm_pattern(bytes, fraction, seed, passes,
+                                      max_chunk_mib << 20, corrupt_word, corrupt_bit));
+}
+
+static py::dict mfma_dict(const MfmaResult& r) {
+  py::dict d;
+  d["tiles"] = r.tiles;
+  d["mismatches"] = r.mismatches;
+  if (r.first_bad < 0) {
+    d["first_bad"] = py::none();
+  } else {
+    d["first_bad"] = py::make_tuple(r.first_bad / 256, r.first_bad / 16 % 16,
+                                    r.first_bad % 16, r.got, r.expected);
+  }
+  return d;
+}
+
+static py::dict mfma_verify(int device, const std::string& dtype, int workgroups,
+                            uint32_t seed, int64_t corrupt_element) {
+  const int dt = parse_dtype(dtype);
+  HIP_CHECK(hipSetDevice(device));
+  return mfma_dict(run_mfma_verify(dt, workgroups, seed, corrupt_element));
+}
+
+typedef std::vector<std::vector<float>> matrix_t;
+
+static py::tuple mfma_verify_tile(int device, const std::string& dtype,
+                                  uint32_t seed, uint32_t workgroup) {
+  const int dt = parse_dtype(dtype);
+  const uint32_t K = (uint32_t)gh::k_of(dt);
+  matrix_t A(16, std::vector<float>(K)), B(K, std::vector<float>(16)),
+      C(16, std::vector<float>(16)), D(16, std::vector<float>(16));
+  for (uint32_t i = 0; i < 16; ++i) {
+    for (uint32_t k = 0; k < K; ++k) {
+      A[i][k] = gh::logical_a(dt, seed, workgroup, i, k);
+      B[k][i] = gh::logical_b(dt, seed, workgroup, k, i);
+    }
+    for (uint32_t c = 0; c < 16; ++c) C[i][c] = (float)gh::gen_c(seed, workgroup, dt, i, c);
+  }
+  HIP_CHECK(hipSetDevice(device));
+  DeviceScope scope;
+  float* d_out = (float*)scope.alloc(256 * sizeof(float));
+  launch_mfma_exact(dt, d_out, 1, seed, workgroup);
+  HIP_CHECK(hipDeviceSynchronize());
+  float host[256];
+  HIP_CHECK(hipMemcpy(host, d_out, sizeof(host), hipMemcpyDeviceToHost));
+  for (int r = 0; r < 16; ++r)
+    for (int c = 0; c < 16; ++c) D[r][c] = host[r * 16 + c];
+  return py::make_tuple(A, B, C, D);
+}
+
+static matrix_t reference_tile_py(const std::string& dtype, uint32_t seed,
+                                  uint32_t workgroup) {
+  float ref[16][16];
+  gh::reference_tile(parse_dtype(dtype), seed, workgroup, ref);
+  matrix_t D(16, std::vector<float>(16));
+  for (int r = 0; r < 16; ++r)
+    for (int c = 0; c < 16; ++c) D[r][c] = ref[r][c];
+  return D;
+}
+
+static const char* const kDtypeNames[gh::kNumDtypes] = {"bf16", "f16", "fp8", "mxfp4"};
+
+static py::dict burn_in(int device, double hbm_fraction, double hbm_floor_gb_s) {
+  py::dict result = health_check(device, hbm_floor_gb_s, false);
+  bool healthy = result["healthy"].cast<bool>();
+  py::dict exact, first_bad;
+  for (int dt = 0; dt < gh::kNumDtypes; ++dt) {
+    const MfmaResult r = run_mfma_verify(dt, 1024, gh::kDefaultSeed, -1);
+    exact[kDtypeNames[dt]] = r.mismatches == 0;
+    first_bad[kDtypeNames[dt]] = mfma_dict(r)["first_bad"];
+    healthy = healthy && r.mismatches == 0;
+  }
+  const PatternResult p = run_hbm_pattern(0, hbm_fraction, gh::kDefaultSeed, 1,
+                                          16384ull << 20, -1, 0);
+  const bool pattern_ok = p.stats.mismatched_words == 0;
+  result["mfma_exact"] = exact;
+  result["mfma_first_bad"] = first_bad;
+  result["hbm_pattern_ok"] = pattern_ok;
+  result["hbm_pattern"] = pattern_dict(p);
+  result["healthy"] = healthy && pattern_ok;
+  return result;
+}
+
 PYBIND11_MODULE(gpuhealth, m) {
-  m.doc() = "MI355X (gfx950) on-device health probes: MFMA smoke + HBM stream";
+  m.doc() = "MI355X (gfx950) on-device health probes: MFMA smoke + HBM stream, "
+            "and the burn-in level (HBM pattern sweep + exact MFMA checks)";
+  m.attr("DEFAULT_SEED") = gh::kDefaultSeed;
+  m.def("pattern_word", &gh::pattern_word, py::arg("seed"), py::arg("word_index"));
+  m.def("reference_tile", &reference_tile_py, py::arg("dtype"), py::arg("seed"),
+        py::arg("workgroup"));
+  m.def("hbm_pattern_check", &hbm_pattern_check, py::arg("device") = 0,
+        py::arg("mib") = 256.0, py::arg("fraction") = 0.0,
+        py::arg("seed") = gh::kDefaultSeed, py::arg("corrupt_word") = -1,
+        py::arg("corrupt_bit") = 0, py::arg("bytes") = 0,
+        py::arg("max_chunk_mib") = 16384, py::arg("passes") = 1);
+  m.def("mfma_verify", &mfma_verify, py::arg("device") = 0, py::arg("dtype") = "bf16",
+        py::arg("workgroups") = 1024, py::arg("seed") = gh::kDefaultSeed,
+        py::arg("corrupt_element") = -1);
+  m.def("mfma_verify_tile", &mfma_verify_tile, py::arg("device") = 0,
+        py::arg("dtype") = "bf16", py::arg("seed") = gh::kDefaultSeed,
+        py::arg("workgroup") = 0);
+  m.def("burn_in", &burn_in, py::arg("device") = 0, py::arg("hbm_fraction") = 0.9,
+        py::arg("hbm_floor_gb_s") = 1000.0);
   m.def("device_count", &device_count);
   m.def("device_info", &device_info, py::arg("device") = 0);
   m.def("mfma_smoke", &mfma_smoke, py::arg("device") = 0,

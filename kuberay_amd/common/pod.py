@@ -16,6 +16,9 @@ these MI355X-native differences:
 * GPU worker readiness probes additionally run an on-device health gate
   (rocm-smi + gfx950 MFMA smoke kernel via ``python -m kuberay_amd.gpu.probe``)
   — the reference has no GPU-level probe at all,
+* a GPU worker template annotated ``amd.com/gpu-burn-in: "true"`` also gets a
+  startupProbe that runs the burn-in level (``probe --deep``: data-verifying
+  HBM sweep + exact MFMA checks),
 * ``/dev/shm`` sizing defaults to the pod memory limit (MI355X hosts are
   large; plasma wants real shm).
 """
@@ -337,6 +340,25 @@ def init_liveness_and_readiness_probe(
         else:
             probe.exec_ = ExecAction(command=["bash", "-c", " && ".join(ready_commands)])
         ray_container.readiness_probe = probe
+
+
+def init_gpu_burn_in_startup_probe(ray_container: Container) -> None:
+    """MI355X burn-in as a startupProbe (opt-in, annotation
+    ``amd.com/gpu-burn-in: "true"`` on a GPU worker template): the HBM
+    pattern sweep and the exact MFMA checks of
+    ``python -m kuberay_amd.gpu.probe --deep`` must pass once before the
+    kubelet starts the liveness and readiness probes, which stay as built.
+    A user-supplied startupProbe is kept."""
+    if ray_container.startup_probe is not None:
+        return
+    probe = Probe(
+        timeout_seconds=C.GPU_BURN_IN_PROBE_TIMEOUT_SECONDS,
+        period_seconds=C.GPU_BURN_IN_PROBE_PERIOD_SECONDS,
+        success_threshold=1,
+        failure_threshold=C.GPU_BURN_IN_PROBE_FAILURE_THRESHOLD,
+    )
+    probe.exec_ = ExecAction(command=["bash", "-c", C.GPU_BURN_IN_PROBE_COMMAND])
+    ray_container.startup_probe = probe
 
 
 # ---------------------------------------------------------------------------
@@ -761,6 +783,10 @@ def build_pod(
         init_liveness_and_readiness_probe(
             ray_container, node_type, creator_crd_type, params, ray_version,
             gpu_probe=gpu_probe)
+        burn_in = (template.metadata.annotations or {}).get(
+            C.GPU_BURN_IN_ANNOTATION_KEY, "").lower() == "true"
+        if gpu_probe and burn_in:
+            init_gpu_burn_in_startup_probe(ray_container)
     return pod
 
 

@@ -10,7 +10,7 @@ from __future__ import annotations
 
 import os
 from dataclasses import dataclass
-from typing import Optional
+from typing import Dict, Optional
 
 from . import rocm_smi
 
@@ -48,6 +48,11 @@ class HealthReport:
     hbm_gb_s: Optional[float] = None
     rocm_smi_ok: Optional[bool] = None
     detail: str = ""
+    # burn-in level only (check_gpu_burn_in); None from the quick/full gate
+    mfma_exact: Optional[Dict[str, bool]] = None
+    hbm_pattern_ok: Optional[bool] = None
+    hbm_bytes_checked: Optional[int] = None
+    hbm_flipped_bits: Optional[int] = None
 
 
 def check_gpu_health(device: int = 0, quick: bool = False,
@@ -77,6 +82,66 @@ def check_gpu_health(device: int = 0, quick: bool = False,
         rocm_smi_ok=rocm_ok,
         detail="" if result["healthy"] else
         f"mfma_ok={result['mfma_ok']} hbm_gb_s={result['hbm_gb_s']:.0f}",
+    )
+
+
+DEFAULT_BURN_IN_HBM_FRACTION = 0.9
+
+
+def check_gpu_burn_in(device: int = 0,
+                      hbm_fraction: float = DEFAULT_BURN_IN_HBM_FRACTION,
+                      hbm_floor_gb_s: float = DEFAULT_HBM_FLOOR_GB_S) -> HealthReport:
+    """Burn-in level: the full gate of ``check_gpu_health``, then the exact
+    MFMA verification on the bf16, f16, fp8 and MXFP4 data paths, then a
+    data-verifying pattern sweep over ``hbm_fraction`` of the free HBM.
+    Raises GpuHealthError on non-GPU hosts; ``detail`` names what failed."""
+    if not gpu_node():
+        raise GpuHealthError("not a GPU node (/dev/kfd missing)")
+    if not 0.0 < hbm_fraction <= 1.0:
+        raise ValueError(f"hbm_fraction must be in (0, 1], got {hbm_fraction}")
+
+    rocm_ok = True
+    try:
+        if not rocm_smi.get_gpu_stats():
+            rocm_ok = False
+    except Exception:
+        rocm_ok = False
+
+    native = _load_native()
+    if native.device_count() <= device:
+        return HealthReport(healthy=False, rocm_smi_ok=rocm_ok,
+                            detail=f"device {device} not visible to HIP")
+    result = native.burn_in(device, hbm_fraction, hbm_floor_gb_s)
+    pattern = result["hbm_pattern"]
+    exact = {k: bool(v) for k, v in result["mfma_exact"].items()}
+
+    problems = []
+    if not result["mfma_ok"] or not result["hbm_ok"]:
+        problems.append(f"mfma_ok={result['mfma_ok']} "
+                        f"hbm_gb_s={result['hbm_gb_s']:.0f}")
+    for dtype, ok in exact.items():
+        if not ok:
+            wg, row, col, got, expected = result["mfma_first_bad"][dtype]
+            problems.append(f"mfma {dtype}: tile {wg} [{row}][{col}] "
+                            f"got {got!r} expected {expected!r}")
+    if not result["hbm_pattern_ok"]:
+        problems.append(
+            f"hbm pattern: {pattern['mismatched_words']} bad words, "
+            f"{pattern['flipped_bits']} flipped bits, mask "
+            f"0x{pattern['bad_bit_mask']:08x}, first bad offset "
+            f"{pattern['first_bad_offset']}")
+    if not rocm_ok:
+        problems.append("rocm-smi did not respond")
+    return HealthReport(
+        healthy=bool(result["healthy"]) and rocm_ok,
+        mfma_ok=bool(result["mfma_ok"]),
+        hbm_gb_s=float(result["hbm_gb_s"]),
+        rocm_smi_ok=rocm_ok,
+        detail="; ".join(problems),
+        mfma_exact=exact,
+        hbm_pattern_ok=bool(result["hbm_pattern_ok"]),
+        hbm_bytes_checked=int(pattern["bytes_checked"]),
+        hbm_flipped_bits=int(pattern["flipped_bits"]),
     )
 
 

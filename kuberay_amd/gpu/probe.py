@@ -2,6 +2,10 @@
 
 Injected into GPU worker readiness probes by the pod builder
 (common/pod.py init_liveness_and_readiness_probe). Exit 0 = healthy.
+
+``--deep [--hbm-fraction F]`` runs the burn-in level instead (HBM pattern
+sweep + exact MFMA checks); the pod builder injects it as a startupProbe on
+GPU workers whose template carries ``amd.com/gpu-burn-in: "true"``.
 """
 from __future__ import annotations
 
@@ -9,7 +13,8 @@ import argparse
 import json
 import sys
 
-from .health import GpuHealthError, check_gpu_health
+from .health import (DEFAULT_BURN_IN_HBM_FRACTION, GpuHealthError,
+                     check_gpu_burn_in, check_gpu_health)
 
 
 def main(argv=None) -> int:
@@ -19,14 +24,44 @@ def main(argv=None) -> int:
     parser.add_argument("--device", type=int, default=0)
     parser.add_argument("--hbm-floor-gb-s", type=float, default=1000.0)
     parser.add_argument("--json", action="store_true", dest="json_out")
+    parser.add_argument("--deep", action="store_true",
+                        help="burn-in level: data-verifying HBM sweep and "
+                             "exact MFMA checks (seconds, for startup probes)")
+    parser.add_argument("--hbm-fraction", type=float,
+                        default=DEFAULT_BURN_IN_HBM_FRACTION,
+                        help="with --deep: fraction of the free HBM to sweep")
     args = parser.parse_args(argv)
 
     try:
-        report = check_gpu_health(device=args.device, quick=args.quick,
-                                  hbm_floor_gb_s=args.hbm_floor_gb_s)
+        if args.deep:
+            report = check_gpu_burn_in(device=args.device,
+                                       hbm_fraction=args.hbm_fraction,
+                                       hbm_floor_gb_s=args.hbm_floor_gb_s)
+        else:
+            report = check_gpu_health(device=args.device, quick=args.quick,
+                                      hbm_floor_gb_s=args.hbm_floor_gb_s)
     except GpuHealthError as e:
         print(f"gpu probe error: {e}", file=sys.stderr)
         return 2
+    if args.deep:
+        if args.json_out:
+            print(json.dumps({
+                "healthy": report.healthy, "mfma_ok": report.mfma_ok,
+                "hbm_gb_s": report.hbm_gb_s, "rocm_smi_ok": report.rocm_smi_ok,
+                "detail": report.detail, "mfma_exact": report.mfma_exact,
+                "hbm_pattern_ok": report.hbm_pattern_ok,
+                "hbm_bytes_checked": report.hbm_bytes_checked,
+                "hbm_flipped_bits": report.hbm_flipped_bits}))
+        else:
+            print(f"healthy={report.healthy} mfma_ok={report.mfma_ok} "
+                  f"hbm_gb_s={report.hbm_gb_s} rocm_smi_ok={report.rocm_smi_ok} "
+                  f"mfma_exact={report.mfma_exact} "
+                  f"hbm_pattern_ok={report.hbm_pattern_ok} "
+                  f"hbm_bytes_checked={report.hbm_bytes_checked} "
+                  f"hbm_flipped_bits={report.hbm_flipped_bits}")
+            if report.detail:
+                print(report.detail, file=sys.stderr)
+        return 0 if report.healthy else 1
     if args.json_out:
         print(json.dumps({
             "healthy": report.healthy, "mfma_ok": report.mfma_ok,

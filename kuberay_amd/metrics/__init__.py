@@ -106,6 +106,15 @@ class OperatorMetrics:
             "1 when the node's GPU telemetry/health probe succeeds, 0 when "
             "it fails (feeds the MI355XGpuUnhealthy alert rule)", ["node"],
             registry=r)
+        self.gpu_burn_in_flipped_bits = Gauge(
+            "kuberay_mi355x_gpu_burn_in_flipped_bits",
+            "Bits that read back wrong in the node's last burn-in HBM "
+            "pattern sweep", ["node"], registry=r)
+        self.gpu_burn_in_ok = Gauge(
+            "kuberay_mi355x_gpu_burn_in_ok",
+            "1 when the named check of the node's last GPU burn-in passed "
+            "(hbm_pattern, mfma_bf16, mfma_f16, mfma_fp8, mfma_mxfp4)",
+            ["node", "check"], registry=r)
 
     # -- hooks used by the reconcilers ----------------------------------
     def observe_cluster_ready(self, cluster) -> None:
@@ -153,6 +162,15 @@ class OperatorMetrics:
 
     def observe_gpu_health(self, node: str, healthy: bool) -> None:
         self.gpu_health.labels(node).set(1 if healthy else 0)
+
+    def observe_gpu_burn_in(self, node: str, report) -> None:
+        """``report`` is a gpu.health.HealthReport from check_gpu_burn_in."""
+        self.gpu_burn_in_flipped_bits.labels(node).set(report.hbm_flipped_bits or 0)
+        self.gpu_burn_in_ok.labels(node, "hbm_pattern").set(
+            1 if report.hbm_pattern_ok else 0)
+        for dtype in ("bf16", "f16", "fp8", "mxfp4"):
+            ok = (report.mfma_exact or {}).get(dtype, False)
+            self.gpu_burn_in_ok.labels(node, f"mfma_{dtype}").set(1 if ok else 0)
 
     def exposition(self) -> bytes:
         return generate_latest(self.registry)

@@ -213,6 +213,23 @@ AMD_GPU_COUNT_LABEL = "amd.com/gpu.count"
 XGMI_FULLY_CONNECTED_LABEL = "amd.com/xgmi-fully-connected"
 XGMI_LARGEST_ISLAND_LABEL = "amd.com/xgmi-largest-island"
 
+# Pod-template annotation: "true" on a GPU worker group's template makes the
+# pod builder add a startupProbe that runs the burn-in level of the health
+# gate (HBM pattern sweep + exact MFMA checks) before the worker may turn
+# Ready. Opt-in; without it the built pod is unchanged.
+GPU_BURN_IN_ANNOTATION_KEY = "amd.com/gpu-burn-in"
+GPU_BURN_IN_PROBE_COMMAND = "python -m kuberay_amd.gpu.probe --deep"
+# Three times the slowest of three measured wall times of the command above on
+# an MI355X at the default HBM fraction (9.27 s, 8.40 s, 8.27 s -> 27.8 s),
+# rounded up to whole seconds: the sweep scales with the free memory and a
+# shared node is slower than an idle one. Measurement: docs/benchmarks.md,
+# "GPU burn-in".
+GPU_BURN_IN_PROBE_TIMEOUT_SECONDS = 28
+GPU_BURN_IN_PROBE_PERIOD_SECONDS = 10
+# A failed burn-in is a finding, not a flake: two attempts, then the
+# container is restarted.
+GPU_BURN_IN_PROBE_FAILURE_THRESHOLD = 2
+
 # Device nodes every ROCm container needs (AMD k8s device plugin mounts these
 # automatically when amd.com/gpu is requested; we also support explicit
 # hostPath injection for clusters without the device plugin).
