@@ -32,7 +32,14 @@
 //                    fp32, through bf16, f16, OCP fp8 and block-scaled MXFP4
 //                    MFMA, with a C input; D is checked element by element
 //                    against integer dot products computed off the matrix
-//                    pipeline. Any lane-routing or operand-bit fault shows.
+//                    pipeline. A lane-routing fault shows (the data is shown
+//                    to expose each of them in tests/test_gpu_probe_kernels.py),
+//                    and so does a fault on an operand bit that the data
+//                    toggles: bf16 bits 15..5, f16 bits 15..8, e4m3 bits 7..1,
+//                    every e2m1 and E8M0 scale bit. The operands are integers
+//                    in [-8, 8], so the low mantissa bits of bf16 (4..0), f16
+//                    (7..0) and fp8 (0) are 0 in every operand: a stuck-at-0
+//                    fault there is outside what this data can show.
 //
 // What must agree between host and device (pattern, generators, encoders,
 // reference) is in gpuhealth_ref.hpp.
@@ -49,6 +56,7 @@
 #include <cstdint>
 #include <stdexcept>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "gpuhealth_ref.hpp"
@@ -119,6 +127,15 @@ __global__ void hbm_stream_kernel(const float4* __restrict__ src,
   }
 }
 
+// The one launch configuration of the stream kernel: ≫256 workgroups to fill
+// 8 XCDs (guide §1); 256 threads/block.
+static void launch_hbm_stream(const float4* d_src, float4* d_dst, size_t n_vec) {
+  const int blocks = 4096;
+  const int threads = 256;
+  hipLaunchKernelGGL(hbm_stream_kernel, dim3(blocks), dim3(threads), 0, 0,
+                     d_src, d_dst, n_vec);
+}
+
 static double run_hbm_stream(size_t bytes, int iters) {
   const size_t n_vec = bytes / sizeof(float4);
   float4 *d_src = nullptr, *d_dst = nullptr;
@@ -126,23 +143,15 @@ static double run_hbm_stream(size_t bytes, int iters) {
   HIP_CHECK(hipMalloc(&d_dst, n_vec * sizeof(float4)));
   HIP_CHECK(hipMemset(d_src, 1, n_vec * sizeof(float4)));
 
-  // ≫256 workgroups to fill 8 XCDs (guide §1); 256 threads/block.
-  const int blocks = 4096;
-  const int threads = 256;
-
   // warmup
-  hipLaunchKernelGGL(hbm_stream_kernel, dim3(blocks), dim3(threads), 0, 0,
-                     d_src, d_dst, n_vec);
+  launch_hbm_stream(d_src, d_dst, n_vec);
   HIP_CHECK(hipDeviceSynchronize());
 
   hipEvent_t t0, t1;
   HIP_CHECK(hipEventCreate(&t0));
   HIP_CHECK(hipEventCreate(&t1));
   HIP_CHECK(hipEventRecord(t0, 0));
-  for (int it = 0; it < iters; ++it) {
-    hipLaunchKernelGGL(hbm_stream_kernel, dim3(blocks), dim3(threads), 0, 0,
-                       d_src, d_dst, n_vec);
-  }
+  for (int it = 0; it < iters; ++it) launch_hbm_stream(d_src, d_dst, n_vec);
   HIP_CHECK(hipEventRecord(t1, 0));
   HIP_CHECK(hipEventSynchronize(t1));
   float ms = 0.f;
@@ -267,20 +276,67 @@ static int pattern_blocks(uint64_t n_vec) {
   return (int)(want < 4096 ? (want ? want : 1) : 4096);
 }
 
+// The one launch configuration of the two sweep kernels; the sweep and every
+// test hook go through these.
+static void launch_pattern_fill(uint4* buf, uint64_t n_vec, uint64_t base_word,
+                                uint32_t seed, uint32_t invert_mask) {
+  hipLaunchKernelGGL(hbm_pattern_fill, dim3(pattern_blocks(n_vec)), dim3(256),
+                     0, 0, buf, n_vec, base_word, seed, invert_mask);
+}
+static void launch_pattern_verify(const uint4* buf, uint64_t n_vec, uint64_t base_word,
+                                  uint32_t seed, uint32_t invert_mask,
+                                  PatternStats* d_stats) {
+  hipLaunchKernelGGL(hbm_pattern_verify, dim3(pattern_blocks(n_vec)), dim3(256),
+                     0, 0, buf, n_vec, base_word, seed, invert_mask, d_stats);
+}
+
 struct PatternResult {
   uint64_t bytes_checked = 0;
   int chunks = 0;
-  PatternStats stats{0, 0, kNoBadWord, 0};
+  PatternStats stats{0, 0, kNoBadWord, 0};  // first_bad_word relative to the sweep
   double gb_s = 0.0;
 };
 
+// (index, xor mask) pairs a test hands in: the host xors the mask into that
+// 32-bit word between a fill / MFMA pass and its check. Signed so that a
+// negative value is reported as a ValueError and not as a conversion error.
+typedef std::vector<std::pair<int64_t, int64_t>> corruptions_t;
+
+// Sorted by index; rejects indices outside [0, limit), masks that are zero or
+// wider than 32 bits, and an index named twice.
+static corruptions_t checked_corruptions(corruptions_t c, uint64_t limit,
+                                         const char* what) {
+  std::sort(c.begin(), c.end());
+  for (size_t n = 0; n < c.size(); ++n) {
+    if (c[n].first < 0 || (uint64_t)c[n].first >= limit)
+      throw py::value_error(std::string(what) + " is outside the checked range");
+    if (c[n].second <= 0 || c[n].second > 0xFFFFFFFFll)
+      throw py::value_error("xor mask must be a non-zero 32-bit value");
+    if (n > 0 && c[n].first == c[n - 1].first)
+      throw py::value_error(std::string(what) + " is named twice");
+  }
+  return c;
+}
+
+// host read-xor-write of one 32-bit word of device memory
+static void xor_device_word(void* addr, uint32_t mask) {
+  uint32_t word = 0;
+  HIP_CHECK(hipMemcpy(&word, addr, 4, hipMemcpyDeviceToHost));
+  word ^= mask;
+  HIP_CHECK(hipMemcpy(addr, &word, 4, hipMemcpyHostToDevice));
+}
+
 // target_bytes > 0: sweep exactly that much; else fraction x free memory.
-// corrupt_word >= 0: the host flips corrupt_bit of that (global) word between
-// the first fill and its verify.
+// pattern_base is added to the word index that feeds the pattern, in the fill
+// and in the verify; everything reported stays relative to the sweep.
+// corruptions: (word, mask) relative to the sweep, applied between the fill and
+// the verify of pass corrupt_pass, phase corrupt_phase.
 static PatternResult run_hbm_pattern(uint64_t target_bytes, double fraction,
                                      uint32_t seed, int passes,
                                      uint64_t max_chunk_bytes,
-                                     int64_t corrupt_word, int corrupt_bit) {
+                                     uint64_t pattern_base = 0,
+                                     corruptions_t corruptions = {},
+                                     int corrupt_pass = 0, int corrupt_phase = 0) {
   if (target_bytes == 0) {
     if (!(fraction > 0.0) || fraction > 1.0)
       throw py::value_error("fraction must be in (0, 1] when no size is given");
@@ -294,9 +350,11 @@ static PatternResult run_hbm_pattern(uint64_t target_bytes, double fraction,
   if (max_chunk_bytes == 0 || max_chunk_bytes % 16 != 0)
     throw py::value_error("chunk size must be a positive multiple of 16 bytes");
   if (passes < 1) throw py::value_error("passes must be >= 1");
-  if (corrupt_bit < 0 || corrupt_bit > 31) throw py::value_error("corrupt_bit must be in [0, 31]");
-  if (corrupt_word < -1 || (corrupt_word >= 0 && (uint64_t)corrupt_word >= target_bytes / 4))
-    throw py::value_error("corrupt_word is outside the swept range");
+  if (pattern_base > ~(uint64_t)0 - target_bytes / 4)
+    throw py::value_error("base_word plus the swept words must fit 64 bits");
+  corruptions = checked_corruptions(std::move(corruptions), target_bytes / 4, "corrupted word");
+  if (corrupt_pass < 0 || corrupt_pass >= passes || corrupt_phase < 0 || corrupt_phase > 1)
+    throw py::value_error("corrupt_at must name a pass in [0, passes) and phase 0 or 1");
 
   struct Chunk { uint4* ptr; uint64_t bytes; uint64_t base_word; };
   DeviceScope scope;
@@ -316,8 +374,8 @@ static PatternResult run_hbm_pattern(uint64_t target_bytes, double fraction,
     covered += want;
   }
   if (chunks.empty()) throw std::runtime_error("could not allocate any device memory to sweep");
-  if (corrupt_word >= 0 && (uint64_t)corrupt_word >= covered / 4)
-    throw py::value_error("corrupt_word is outside the memory that could be allocated");
+  if (!corruptions.empty() && (uint64_t)corruptions.back().first >= covered / 4)
+    throw py::value_error("corrupted word is outside the memory that could be allocated");
 
   PatternStats* d_stats = (PatternStats*)scope.alloc(sizeof(PatternStats));
   PatternResult res;
@@ -329,28 +387,22 @@ static PatternResult run_hbm_pattern(uint64_t target_bytes, double fraction,
     // moving inversion: every bit is driven to 0 and to 1 and read back
     for (int phase = 0; phase < 2; ++phase) {
       const uint32_t inv = phase ? 0xFFFFFFFFu : 0u;
-      for (const Chunk& c : chunks) {
-        const uint64_t n_vec = c.bytes / 16;
-        hipLaunchKernelGGL(hbm_pattern_fill, dim3(pattern_blocks(n_vec)), dim3(256),
-                           0, 0, c.ptr, n_vec, c.base_word, seed, inv);
-      }
+      for (const Chunk& c : chunks)
+        launch_pattern_fill(c.ptr, c.bytes / 16, pattern_base + c.base_word, seed, inv);
       HIP_CHECK(hipGetLastError());
-      if (corrupt_word >= 0 && pass == 0 && phase == 0) {
-        for (const Chunk& c : chunks) {
-          const uint64_t w = (uint64_t)corrupt_word;
-          if (w < c.base_word || w >= c.base_word + c.bytes / 4) continue;
-          uint32_t* addr = (uint32_t*)c.ptr + (w - c.base_word);
-          uint32_t word = 0;
-          HIP_CHECK(hipMemcpy(&word, addr, 4, hipMemcpyDeviceToHost));
-          word ^= 1u << corrupt_bit;
-          HIP_CHECK(hipMemcpy(addr, &word, 4, hipMemcpyHostToDevice));
+      if (pass == corrupt_pass && phase == corrupt_phase) {
+        // both lists are sorted, so one walk finds every word's chunk
+        size_t ci = 0;
+        for (const auto& [word, mask] : corruptions) {
+          const uint64_t w = (uint64_t)word;
+          while (w >= chunks[ci].base_word + chunks[ci].bytes / 4) ++ci;
+          xor_device_word((uint32_t*)chunks[ci].ptr + (w - chunks[ci].base_word),
+                          (uint32_t)mask);
         }
       }
-      for (const Chunk& c : chunks) {
-        const uint64_t n_vec = c.bytes / 16;
-        hipLaunchKernelGGL(hbm_pattern_verify, dim3(pattern_blocks(n_vec)), dim3(256),
-                           0, 0, c.ptr, n_vec, c.base_word, seed, inv, d_stats);
-      }
+      for (const Chunk& c : chunks)
+        launch_pattern_verify(c.ptr, c.bytes / 16, pattern_base + c.base_word, seed, inv,
+                              d_stats);
       HIP_CHECK(hipGetLastError());
     }
   }
@@ -359,10 +411,73 @@ static PatternResult run_hbm_pattern(uint64_t target_bytes, double fraction,
   float ms = 0.f;
   HIP_CHECK(hipEventElapsedTime(&ms, t0, t1));
   HIP_CHECK(hipMemcpy(&res.stats, d_stats, sizeof(PatternStats), hipMemcpyDeviceToHost));
+  // the kernels see pattern indices; pattern_base + words fits 64 bits (above),
+  // so the smallest pattern index is the smallest sweep word
+  if (res.stats.first_bad_word != kNoBadWord) res.stats.first_bad_word -= pattern_base;
   res.bytes_checked = covered;
   res.chunks = (int)chunks.size();
   // per pass: two fills (write) and two verifies (read) of every byte
   res.gb_s = ms > 0.f ? 4.0 * (double)covered * passes / (ms * 1e-3) / 1e9 : 0.0;
+  return res;
+}
+
+// -- test hooks: what the kernels above leave in memory -----------------------
+static constexpr uint64_t kDebugMaxBytes = 256ull << 20;
+
+// One buffer, one production fill, read back raw. The buffer is preset so that
+// a vector the fill skips reads back as 0x5A bytes and not as stale memory.
+static std::string run_debug_pattern_fill(uint64_t bytes, uint32_t seed, bool invert,
+                                          uint64_t base_word) {
+  if (bytes == 0 || bytes % 16 != 0 || bytes > kDebugMaxBytes)
+    throw py::value_error("bytes must be a positive multiple of 16, at most 256 MiB");
+  if (base_word > ~(uint64_t)0 - bytes / 4)
+    throw py::value_error("base_word plus the filled words must fit 64 bits");
+  DeviceScope scope;
+  uint4* d_buf = (uint4*)scope.alloc(bytes);
+  HIP_CHECK(hipMemset(d_buf, 0x5A, bytes));
+  launch_pattern_fill(d_buf, bytes / 16, base_word, seed, invert ? 0xFFFFFFFFu : 0u);
+  HIP_CHECK(hipGetLastError());
+  HIP_CHECK(hipDeviceSynchronize());
+  std::string host(bytes, '\0');
+  HIP_CHECK(hipMemcpy(&host[0], d_buf, bytes, hipMemcpyDeviceToHost));
+  return host;
+}
+
+struct StreamCopyResult {
+  PatternResult pattern;
+  bool guard_intact = false;
+};
+
+// src holds the pattern, dst a sentinel; one production launch of the stream
+// kernel; then the production verify reads dst. Both buffers are one vector
+// longer than the copy: src's extra vector is zero, dst's is the guard, so a
+// copy that runs one vector long overwrites the guard and still stays inside
+// both allocations.
+static StreamCopyResult run_debug_stream_copy(uint64_t bytes, uint32_t seed) {
+  const uint64_t n_vec = bytes / 16;
+  if (n_vec == 0 || bytes > kDebugMaxBytes)
+    throw py::value_error("bytes must be at least 16 and at most 256 MiB");
+  constexpr int kSentinel = 0xA5;
+  DeviceScope scope;
+  uint4* d_src = (uint4*)scope.alloc((n_vec + 1) * 16);
+  uint4* d_dst = (uint4*)scope.alloc((n_vec + 1) * 16);
+  PatternStats* d_stats = (PatternStats*)scope.alloc(sizeof(PatternStats));
+  StreamCopyResult res;
+  HIP_CHECK(hipMemcpy(d_stats, &res.pattern.stats, sizeof(PatternStats), hipMemcpyHostToDevice));
+  HIP_CHECK(hipMemset(d_src, 0, (n_vec + 1) * 16));
+  HIP_CHECK(hipMemset(d_dst, kSentinel, (n_vec + 1) * 16));
+  launch_pattern_fill(d_src, n_vec, 0, seed, 0u);
+  launch_hbm_stream((const float4*)d_src, (float4*)d_dst, n_vec);
+  launch_pattern_verify(d_dst, n_vec, 0, seed, 0u, d_stats);
+  HIP_CHECK(hipGetLastError());
+  HIP_CHECK(hipDeviceSynchronize());
+  HIP_CHECK(hipMemcpy(&res.pattern.stats, d_stats, sizeof(PatternStats), hipMemcpyDeviceToHost));
+  unsigned char guard[16];
+  HIP_CHECK(hipMemcpy(guard, d_dst + n_vec, sizeof(guard), hipMemcpyDeviceToHost));
+  res.guard_intact = std::all_of(guard, guard + sizeof(guard),
+                                 [](unsigned char b) { return b == kSentinel; });
+  res.pattern.bytes_checked = 16 * n_vec;
+  res.pattern.chunks = 1;
   return res;
 }
 
@@ -376,8 +491,9 @@ static PatternResult run_hbm_pattern(uint64_t target_bytes, double fraction,
 //                         k = 32g + j, the even element in the low nibble; the
 //                         lane's scale byte is the E8M0 of (row/col i, block g)
 //   C/D (all paths)     : register r = D[4g + r][i]
-// The maps are proven on the device by tests/test_gpu_burn_in.py: with
-// asymmetric hashed data D equals A·B + C exactly only if all are right.
+// The maps are proven on the device by tests/test_gpu_burn_in.py and
+// tests/test_gpu_probe_kernels.py: with asymmetric hashed data D equals
+// A·B + C exactly only if all are right.
 // ---------------------------------------------------------------------------
 typedef __attribute__((ext_vector_type(8))) _Float16 frag_f16_t;
 typedef __attribute__((ext_vector_type(8))) int frag_i32x8_t;
@@ -504,15 +620,14 @@ struct MfmaResult {
   float got = 0.f, expected = 0.f;
 };
 
-// corrupt_element >= 0: the host flips one mantissa bit of that element of D
+// corruptions: the host xors each mask into that element of D
 // ((workgroup * 16 + row) * 16 + col) between the MFMA pass and the check.
 static MfmaResult run_mfma_verify(int dtype, int workgroups, uint32_t seed,
-                                  int64_t corrupt_element) {
+                                  corruptions_t corruptions = {}) {
   if (workgroups < 1 || workgroups > (1 << 20))
     throw py::value_error("workgroups must be in [1, 2^20]");
   const size_t n = (size_t)workgroups * 256;
-  if (corrupt_element < -1 || (corrupt_element >= 0 && (uint64_t)corrupt_element >= n))
-    throw py::value_error("corrupt_element is outside the output buffer");
+  corruptions = checked_corruptions(std::move(corruptions), n, "corrupted element");
 
   DeviceScope scope;
   float* d_out = (float*)scope.alloc(n * sizeof(float));
@@ -521,12 +636,8 @@ static MfmaResult run_mfma_verify(int dtype, int workgroups, uint32_t seed,
   HIP_CHECK(hipMemcpy(d_stats, &st, sizeof(st), hipMemcpyHostToDevice));
 
   launch_mfma_exact(dtype, d_out, workgroups, seed, 0);
-  if (corrupt_element >= 0) {
-    uint32_t word = 0;
-    HIP_CHECK(hipMemcpy(&word, d_out + corrupt_element, 4, hipMemcpyDeviceToHost));
-    word ^= 1u << 20;
-    HIP_CHECK(hipMemcpy(d_out + corrupt_element, &word, 4, hipMemcpyHostToDevice));
-  }
+  for (const auto& [element, mask] : corruptions)
+    xor_device_word(d_out + element, (uint32_t)mask);
   hipLaunchKernelGGL(mfma_check_kernel, dim3(workgroups), dim3(64), 0, 0,
                      d_out, dtype, seed, 0u, d_stats);
   HIP_CHECK(hipGetLastError());
@@ -544,6 +655,21 @@ static MfmaResult run_mfma_verify(int dtype, int workgroups, uint32_t seed,
                                          (uint32_t)(st.first_bad % 16));
   }
   return res;
+}
+
+// test hook: the raw fp32 D buffer of the production MFMA pass
+static std::string run_debug_mfma_dump(int dtype, int workgroups, uint32_t seed) {
+  if (workgroups < 1 || workgroups > 4096)
+    throw py::value_error("workgroups must be in [1, 4096]");
+  const size_t bytes = (size_t)workgroups * 256 * sizeof(float);
+  DeviceScope scope;
+  float* d_out = (float*)scope.alloc(bytes);
+  HIP_CHECK(hipMemset(d_out, 0xFF, bytes));  // an unwritten element reads as NaN
+  launch_mfma_exact(dtype, d_out, workgroups, seed, 0);
+  HIP_CHECK(hipDeviceSynchronize());
+  std::string host(bytes, '\0');
+  HIP_CHECK(hipMemcpy(&host[0], d_out, bytes, hipMemcpyDeviceToHost));
+  return host;
 }
 
 // ---------------------------------------------------------------------------
@@ -618,19 +744,41 @@ static py::dict pattern_dict(const PatternResult& r) {
   return d;
 }
 
+// corrupt_word >= 0 with corrupt_bit is shorthand for
+// corruptions = [(corrupt_word, 1 << corrupt_bit)]
 static py::dict hbm_pattern_check(int device, double mib, double fraction,
                                   uint32_t seed, int64_t corrupt_word,
                                   int corrupt_bit, uint64_t bytes,
-                                  uint64_t max_chunk_mib, int passes) {
+                                  uint64_t max_chunk_mib, int passes,
+                                  uint64_t base_word, corruptions_t corruptions,
+                                  std::pair<int, int> corrupt_at) {
   if (bytes == 0 && fraction == 0.0) {
     if (!(mib > 0.0)) throw py::value_error("mib must be positive");
     bytes = (uint64_t)(mib * 1048576.0) & ~(uint64_t)15;
   }
   if (max_chunk_mib == 0 || max_chunk_mib > 16384)
     throw py::value_error("max_chunk_mib must be in [1, 16384]");
+  if (corrupt_bit < 0 || corrupt_bit > 31) throw py::value_error("corrupt_bit must be in [0, 31]");
+  if (corrupt_word < -1) throw py::value_error("corrupt_word is outside the swept range");
+  if (corrupt_word >= 0) corruptions.emplace_back(corrupt_word, (int64_t)1 << corrupt_bit);
   HIP_CHECK(hipSetDevice(device));
-  return pattern_dict(run_hbm_pattern(bytes, fraction, seed, passes,
-                                      max_chunk_mib << 20, corrupt_word, corrupt_bit));
+  return pattern_dict(run_hbm_pattern(bytes, fraction, seed, passes, max_chunk_mib << 20,
+                                      base_word, std::move(corruptions),
+                                      corrupt_at.first, corrupt_at.second));
+}
+
+static py::bytes debug_pattern_fill(int device, uint64_t bytes, uint32_t seed,
+                                    bool invert, uint64_t base_word) {
+  HIP_CHECK(hipSetDevice(device));
+  return py::bytes(run_debug_pattern_fill(bytes, seed, invert, base_word));
+}
+
+static py::dict debug_stream_copy_check(int device, uint64_t bytes, uint32_t seed) {
+  HIP_CHECK(hipSetDevice(device));
+  const StreamCopyResult r = run_debug_stream_copy(bytes, seed);
+  py::dict d = pattern_dict(r.pattern);
+  d["guard_intact"] = r.guard_intact;
+  return d;
 }
 
 static py::dict mfma_dict(const MfmaResult& r) {
@@ -646,11 +794,23 @@ static py::dict mfma_dict(const MfmaResult& r) {
   return d;
 }
 
+// corrupt_element >= 0 is shorthand for corruptions = [(corrupt_element,
+// 1 << 20)], one mantissa bit
 static py::dict mfma_verify(int device, const std::string& dtype, int workgroups,
-                            uint32_t seed, int64_t corrupt_element) {
+                            uint32_t seed, int64_t corrupt_element,
+                            corruptions_t corruptions) {
+  const int dt = parse_dtype(dtype);
+  if (corrupt_element < -1) throw py::value_error("corrupt_element is outside the output buffer");
+  if (corrupt_element >= 0) corruptions.emplace_back(corrupt_element, (int64_t)1 << 20);
+  HIP_CHECK(hipSetDevice(device));
+  return mfma_dict(run_mfma_verify(dt, workgroups, seed, std::move(corruptions)));
+}
+
+static py::bytes debug_mfma_dump(int device, const std::string& dtype, int workgroups,
+                                 uint32_t seed) {
   const int dt = parse_dtype(dtype);
   HIP_CHECK(hipSetDevice(device));
-  return mfma_dict(run_mfma_verify(dt, workgroups, seed, corrupt_element));
+  return py::bytes(run_debug_mfma_dump(dt, workgroups, seed));
 }
 
 typedef std::vector<std::vector<float>> matrix_t;
@@ -697,13 +857,13 @@ static py::dict burn_in(int device, double hbm_fraction, double hbm_floor_gb_s) 
   bool healthy = result["healthy"].cast<bool>();
   py::dict exact, first_bad;
   for (int dt = 0; dt < gh::kNumDtypes; ++dt) {
-    const MfmaResult r = run_mfma_verify(dt, 1024, gh::kDefaultSeed, -1);
+    const MfmaResult r = run_mfma_verify(dt, 1024, gh::kDefaultSeed);
     exact[kDtypeNames[dt]] = r.mismatches == 0;
     first_bad[kDtypeNames[dt]] = mfma_dict(r)["first_bad"];
     healthy = healthy && r.mismatches == 0;
   }
   const PatternResult p = run_hbm_pattern(0, hbm_fraction, gh::kDefaultSeed, 1,
-                                          16384ull << 20, -1, 0);
+                                          16384ull << 20);
   const bool pattern_ok = p.stats.mismatched_words == 0;
   result["mfma_exact"] = exact;
   result["mfma_first_bad"] = first_bad;
@@ -724,10 +884,22 @@ PYBIND11_MODULE(gpuhealth, m) {
         py::arg("mib") = 256.0, py::arg("fraction") = 0.0,
         py::arg("seed") = gh::kDefaultSeed, py::arg("corrupt_word") = -1,
         py::arg("corrupt_bit") = 0, py::arg("bytes") = 0,
-        py::arg("max_chunk_mib") = 16384, py::arg("passes") = 1);
+        py::arg("max_chunk_mib") = 16384, py::arg("passes") = 1,
+        py::arg("base_word") = 0, py::arg("corruptions") = corruptions_t{},
+        py::arg("corrupt_at") = std::pair<int, int>(0, 0));
   m.def("mfma_verify", &mfma_verify, py::arg("device") = 0, py::arg("dtype") = "bf16",
         py::arg("workgroups") = 1024, py::arg("seed") = gh::kDefaultSeed,
-        py::arg("corrupt_element") = -1);
+        py::arg("corrupt_element") = -1, py::arg("corruptions") = corruptions_t{});
+  // test hooks: the production kernels through the production launch code,
+  // with what they wrote handed back
+  m.def("debug_pattern_fill", &debug_pattern_fill, py::arg("device") = 0,
+        py::arg("bytes") = 4096, py::arg("seed") = gh::kDefaultSeed,
+        py::arg("invert") = false, py::arg("base_word") = 0);
+  m.def("debug_stream_copy_check", &debug_stream_copy_check, py::arg("device") = 0,
+        py::arg("bytes") = 4096, py::arg("seed") = gh::kDefaultSeed);
+  m.def("debug_mfma_dump", &debug_mfma_dump, py::arg("device") = 0,
+        py::arg("dtype") = "bf16", py::arg("workgroups") = 64,
+        py::arg("seed") = gh::kDefaultSeed);
   m.def("mfma_verify_tile", &mfma_verify_tile, py::arg("device") = 0,
         py::arg("dtype") = "bf16", py::arg("seed") = gh::kDefaultSeed,
         py::arg("workgroup") = 0);

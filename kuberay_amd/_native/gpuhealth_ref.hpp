@@ -13,6 +13,12 @@
 // a multiple of 1/16 below 2^15. Both fit the 24-bit fp32 significand, hence
 // every accumulation order gives the same fp32 result and the device's D can
 // be compared with == against integer arithmetic.
+//
+// What the premise costs: integers in [-8, 8] leave the low mantissa bits of
+// every bf16 (bits 4..0), f16 (bits 7..0) and e4m3 (bit 0) operand at 0, so a
+// stuck-at-0 fault on those operand bits is outside what the data can show.
+// Every other operand bit, every e2m1 bit and every E8M0 scale bit takes both
+// values (tests/test_gpu_probe_kernels.py).
 #pragma once
 
 #include <cstdint>

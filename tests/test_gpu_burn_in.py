@@ -36,67 +36,11 @@ def native():
 
 
 # ---------------------------------------------------------------------------
-# Python transcription of gpuhealth_ref.hpp (pattern + generators)
+# Python transcription of gpuhealth_ref.hpp (pattern + generators): shared with
+# tests/test_gpu_probe_kernels.py, in tests/gpuhealth_model.py
 # ---------------------------------------------------------------------------
-M32 = 0xFFFFFFFF
-
-
-def _mix32(x):
-    x ^= x >> 16
-    x = (x * 0x7FEB352D) & M32
-    x ^= x >> 15
-    x = (x * 0x846CA68B) & M32
-    x ^= x >> 16
-    return x
-
-
-def _pattern_word(seed, index):
-    lo, hi = index & M32, index >> 32
-    x = (lo + seed * 0x9E3779B9) & M32
-    x ^= (hi * 0x85EBCA6B) & M32
-    return _mix32(x)
-
-
-DT_INDEX = {"bf16": 0, "f16": 1, "fp8": 2, "mxfp4": 3}
-GEN_A, GEN_B, GEN_C, GEN_SA, GEN_SB = range(5)
-E2M1 = (0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0)
-
-
-def _elem_hash(seed, wg, dtype, which, i, k):
-    h = _mix32(seed ^ (((wg + 1) * 0x9E3779B9) & M32))
-    return _mix32(h ^ (((DT_INDEX[dtype] * 8 + which) << 24) & M32) ^ (i << 8) ^ k)
-
-
-def _gen_int(seed, wg, dtype, which, i, k):
-    return ((_elem_hash(seed, wg, dtype, which, i, k) >> 8) % 17) - 8
-
-
-def _gen_fp4(seed, wg, which, i, k):
-    code = (_elem_hash(seed, wg, "mxfp4", which, i, k) >> 8) & 15
-    return -E2M1[code & 7] if code & 8 else E2M1[code & 7]
-
-
-def _gen_scale(seed, wg, which, i, block):
-    e8m0 = 126 + ((_elem_hash(seed, wg, "mxfp4", which, i, block) >> 8) % 3)
-    return 2.0 ** (e8m0 - 127)
-
-
-def _operands(dtype, seed, wg):
-    K = 128 if dtype == "mxfp4" else 32
-    A = np.zeros((16, K))
-    B = np.zeros((K, 16))
-    C_ = np.zeros((16, 16))
-    for i in range(16):
-        for k in range(K):
-            if dtype == "mxfp4":
-                A[i, k] = _gen_fp4(seed, wg, GEN_A, i, k) * _gen_scale(seed, wg, GEN_SA, i, k // 32)
-                B[k, i] = _gen_fp4(seed, wg, GEN_B, i, k) * _gen_scale(seed, wg, GEN_SB, i, k // 32)
-            else:
-                A[i, k] = _gen_int(seed, wg, dtype, GEN_A, i, k)
-                B[k, i] = _gen_int(seed, wg, dtype, GEN_B, i, k)
-        for c in range(16):
-            C_[i, c] = _gen_int(seed, wg, dtype, GEN_C, i, c)
-    return A, B, C_
+from gpuhealth_model import operands as _operands          # noqa: E402
+from gpuhealth_model import pattern_word as _pattern_word  # noqa: E402
 
 
 # ---------------------------------------------------------------------------
