@@ -13,6 +13,12 @@
 //                    with all-ones inputs; every D element must equal K=32.
 //                    Proves the matrix pipeline executes and returns. All-ones
 //                    data is blind to lane routing and to low operand bits.
+//                    The output buffer is preset to 0xFF bytes (NaN) before
+//                    the launch, so an element the kernel did not write fails
+//                    the exact host compare whatever the allocator handed
+//                    back. Test hooks: mfma_smoke(corruptions=,
+//                    launch_workgroups=) and debug_mfma_smoke_dump (the raw
+//                    buffer of the same code path).
 //   * hbm_stream   — float4 streaming copy sized ≫ L3 (256 MiB) across
 //                    ≫256 workgroups; host computes GB/s and compares
 //                    against a floor (healthy MI355X streams ≈6 TB/s; a
@@ -73,6 +79,78 @@ namespace py = pybind11;
   } while (0)
 
 // ---------------------------------------------------------------------------
+// host helpers shared by every probe
+// ---------------------------------------------------------------------------
+static int device_count() {
+  int n = 0;
+  hipError_t e = hipGetDeviceCount(&n);
+  if (e != hipSuccess) return 0;
+  return n;
+}
+
+// Every binding that takes a device ordinal goes through here: an ordinal that
+// does not name a visible device is a ValueError like every other bad
+// argument, not whatever hipSetDevice makes of it.
+static void use_device(int device) {
+  const int count = device_count();
+  if (device < 0 || device >= count)
+    throw py::value_error("device " + std::to_string(device) + " is outside [0, " +
+                          std::to_string(count) + "), the devices visible to HIP");
+  HIP_CHECK(hipSetDevice(device));
+}
+
+// Frees every device allocation and event it was handed, on every path out.
+struct DeviceScope {
+  std::vector<void*> ptrs;
+  std::vector<hipEvent_t> events;
+  ~DeviceScope() {
+    for (hipEvent_t e : events) (void)hipEventDestroy(e);
+    for (void* p : ptrs) (void)hipFree(p);
+  }
+  void* alloc(size_t bytes) {
+    void* p = nullptr;
+    HIP_CHECK(hipMalloc(&p, bytes));
+    ptrs.push_back(p);
+    return p;
+  }
+  hipEvent_t event() {
+    hipEvent_t e;
+    HIP_CHECK(hipEventCreate(&e));
+    events.push_back(e);
+    return e;
+  }
+};
+
+// (index, xor mask) pairs a test hands in: the host xors the mask into that
+// 32-bit word between a fill / MFMA pass and its check. Signed so that a
+// negative value is reported as a ValueError and not as a conversion error.
+typedef std::vector<std::pair<int64_t, int64_t>> corruptions_t;
+
+// Sorted by index; rejects indices outside [0, limit), masks that are zero or
+// wider than 32 bits, and an index named twice.
+static corruptions_t checked_corruptions(corruptions_t c, uint64_t limit,
+                                         const char* what) {
+  std::sort(c.begin(), c.end());
+  for (size_t n = 0; n < c.size(); ++n) {
+    if (c[n].first < 0 || (uint64_t)c[n].first >= limit)
+      throw py::value_error(std::string(what) + " is outside the checked range");
+    if (c[n].second <= 0 || c[n].second > 0xFFFFFFFFll)
+      throw py::value_error("xor mask must be a non-zero 32-bit value");
+    if (n > 0 && c[n].first == c[n - 1].first)
+      throw py::value_error(std::string(what) + " is named twice");
+  }
+  return c;
+}
+
+// host read-xor-write of one 32-bit word of device memory
+static void xor_device_word(void* addr, uint32_t mask) {
+  uint32_t word = 0;
+  HIP_CHECK(hipMemcpy(&word, addr, 4, hipMemcpyDeviceToHost));
+  word ^= mask;
+  HIP_CHECK(hipMemcpy(addr, &word, 4, hipMemcpyHostToDevice));
+}
+
+// ---------------------------------------------------------------------------
 // MFMA smoke: D = A(1s) * B(1s) + 0  ->  every element == K == 32
 // ---------------------------------------------------------------------------
 #if defined(__HIP_DEVICE_COMPILE__) && !defined(__gfx950__)
@@ -99,18 +177,38 @@ __global__ void mfma_smoke_kernel(float* __restrict__ out) {
   }
 }
 
-static bool run_mfma_smoke(int workgroups) {
+// The buffer is preset to 0xFF bytes (NaN): hipMalloc hands a freed block of
+// the same size back, still holding the 32.0f of the previous good run, so
+// without the preset a launch that wrote only part of the buffer would pass.
+// corruptions: the host xors each mask into that element between the kernel
+// and the check. launch_workgroups (test hook): -1 launches every tile, a
+// value in [0, workgroups] only that many while the check still covers
+// workgroups; 0 skips the launch. raw, when given, receives the checked buffer.
+static bool run_mfma_smoke(int workgroups, corruptions_t corruptions = {},
+                           int launch_workgroups = -1, std::string* raw = nullptr) {
+  if (workgroups < 1 || workgroups > (1 << 20))
+    throw py::value_error("workgroups must be in [1, 2^20]");
+  if (launch_workgroups < -1 || launch_workgroups > workgroups)
+    throw py::value_error("launch_workgroups must be -1 or in [0, workgroups]");
   const size_t n = (size_t)workgroups * 256;
-  float* d_out = nullptr;
-  HIP_CHECK(hipMalloc(&d_out, n * sizeof(float)));
-  hipLaunchKernelGGL(mfma_smoke_kernel, dim3(workgroups), dim3(64), 0, 0, d_out);
-  HIP_CHECK(hipGetLastError());
+  corruptions = checked_corruptions(std::move(corruptions), n, "corrupted element");
+
+  DeviceScope scope;
+  float* d_out = (float*)scope.alloc(n * sizeof(float));
+  HIP_CHECK(hipMemset(d_out, 0xFF, n * sizeof(float)));
+  const int launched = launch_workgroups < 0 ? workgroups : launch_workgroups;
+  if (launched > 0) {
+    hipLaunchKernelGGL(mfma_smoke_kernel, dim3(launched), dim3(64), 0, 0, d_out);
+    HIP_CHECK(hipGetLastError());
+  }
   HIP_CHECK(hipDeviceSynchronize());
+  for (const auto& [element, mask] : corruptions)
+    xor_device_word(d_out + element, (uint32_t)mask);
   std::vector<float> host(n);
   HIP_CHECK(hipMemcpy(host.data(), d_out, n * sizeof(float), hipMemcpyDeviceToHost));
-  HIP_CHECK(hipFree(d_out));
+  if (raw) raw->assign((const char*)host.data(), n * sizeof(float));
   for (size_t i = 0; i < n; ++i) {
-    if (host[i] != 32.0f) return false;
+    if (host[i] != 32.0f) return false;  // exact, and true for a NaN
   }
   return true;
 }
@@ -138,28 +236,22 @@ static void launch_hbm_stream(const float4* d_src, float4* d_dst, size_t n_vec) 
 
 static double run_hbm_stream(size_t bytes, int iters) {
   const size_t n_vec = bytes / sizeof(float4);
-  float4 *d_src = nullptr, *d_dst = nullptr;
-  HIP_CHECK(hipMalloc(&d_src, n_vec * sizeof(float4)));
-  HIP_CHECK(hipMalloc(&d_dst, n_vec * sizeof(float4)));
+  DeviceScope scope;  // up to 4 GiB per buffer: freed on a throwing HIP_CHECK too
+  float4* d_src = (float4*)scope.alloc(n_vec * sizeof(float4));
+  float4* d_dst = (float4*)scope.alloc(n_vec * sizeof(float4));
   HIP_CHECK(hipMemset(d_src, 1, n_vec * sizeof(float4)));
 
   // warmup
   launch_hbm_stream(d_src, d_dst, n_vec);
   HIP_CHECK(hipDeviceSynchronize());
 
-  hipEvent_t t0, t1;
-  HIP_CHECK(hipEventCreate(&t0));
-  HIP_CHECK(hipEventCreate(&t1));
+  hipEvent_t t0 = scope.event(), t1 = scope.event();
   HIP_CHECK(hipEventRecord(t0, 0));
   for (int it = 0; it < iters; ++it) launch_hbm_stream(d_src, d_dst, n_vec);
   HIP_CHECK(hipEventRecord(t1, 0));
   HIP_CHECK(hipEventSynchronize(t1));
   float ms = 0.f;
   HIP_CHECK(hipEventElapsedTime(&ms, t0, t1));
-  HIP_CHECK(hipEventDestroy(t0));
-  HIP_CHECK(hipEventDestroy(t1));
-  HIP_CHECK(hipFree(d_src));
-  HIP_CHECK(hipFree(d_dst));
   // read + write traffic
   const double total_bytes = 2.0 * (double)n_vec * sizeof(float4) * iters;
   return total_bytes / (ms * 1e-3) / 1e9;  // GB/s
@@ -248,28 +340,6 @@ __global__ void hbm_pattern_verify(const uint4* __restrict__ buf, uint64_t n_vec
   }
 }
 
-// Frees every device allocation and event it was handed, on every path out.
-struct DeviceScope {
-  std::vector<void*> ptrs;
-  std::vector<hipEvent_t> events;
-  ~DeviceScope() {
-    for (hipEvent_t e : events) (void)hipEventDestroy(e);
-    for (void* p : ptrs) (void)hipFree(p);
-  }
-  void* alloc(size_t bytes) {
-    void* p = nullptr;
-    HIP_CHECK(hipMalloc(&p, bytes));
-    ptrs.push_back(p);
-    return p;
-  }
-  hipEvent_t event() {
-    hipEvent_t e;
-    HIP_CHECK(hipEventCreate(&e));
-    events.push_back(e);
-    return e;
-  }
-};
-
 static int pattern_blocks(uint64_t n_vec) {
   // ≫256 workgroups to fill 8 XCDs, as the stream kernel; fewer for tiny runs
   const uint64_t want = (n_vec + 255) / 256;
@@ -296,35 +366,6 @@ struct PatternResult {
   PatternStats stats{0, 0, kNoBadWord, 0};  // first_bad_word relative to the sweep
   double gb_s = 0.0;
 };
-
-// (index, xor mask) pairs a test hands in: the host xors the mask into that
-// 32-bit word between a fill / MFMA pass and its check. Signed so that a
-// negative value is reported as a ValueError and not as a conversion error.
-typedef std::vector<std::pair<int64_t, int64_t>> corruptions_t;
-
-// Sorted by index; rejects indices outside [0, limit), masks that are zero or
-// wider than 32 bits, and an index named twice.
-static corruptions_t checked_corruptions(corruptions_t c, uint64_t limit,
-                                         const char* what) {
-  std::sort(c.begin(), c.end());
-  for (size_t n = 0; n < c.size(); ++n) {
-    if (c[n].first < 0 || (uint64_t)c[n].first >= limit)
-      throw py::value_error(std::string(what) + " is outside the checked range");
-    if (c[n].second <= 0 || c[n].second > 0xFFFFFFFFll)
-      throw py::value_error("xor mask must be a non-zero 32-bit value");
-    if (n > 0 && c[n].first == c[n - 1].first)
-      throw py::value_error(std::string(what) + " is named twice");
-  }
-  return c;
-}
-
-// host read-xor-write of one 32-bit word of device memory
-static void xor_device_word(void* addr, uint32_t mask) {
-  uint32_t word = 0;
-  HIP_CHECK(hipMemcpy(&word, addr, 4, hipMemcpyDeviceToHost));
-  word ^= mask;
-  HIP_CHECK(hipMemcpy(addr, &word, 4, hipMemcpyHostToDevice));
-}
 
 // target_bytes > 0: sweep exactly that much; else fraction x free memory.
 // pattern_base is added to the word index that feeds the pattern, in the fill
@@ -675,15 +716,8 @@ static std::string run_debug_mfma_dump(int dtype, int workgroups, uint32_t seed)
 // ---------------------------------------------------------------------------
 // host API
 // ---------------------------------------------------------------------------
-static int device_count() {
-  int n = 0;
-  hipError_t e = hipGetDeviceCount(&n);
-  if (e != hipSuccess) return 0;
-  return n;
-}
-
 static py::dict device_info(int device) {
-  HIP_CHECK(hipSetDevice(device));
+  use_device(device);
   hipDeviceProp_t prop;
   HIP_CHECK(hipGetDeviceProperties(&prop, device));
   py::dict d;
@@ -696,13 +730,24 @@ static py::dict device_info(int device) {
   return d;
 }
 
-static bool mfma_smoke(int device, int workgroups) {
-  HIP_CHECK(hipSetDevice(device));
-  return run_mfma_smoke(workgroups);
+static bool mfma_smoke(int device, int workgroups, corruptions_t corruptions,
+                       int launch_workgroups) {
+  use_device(device);
+  return run_mfma_smoke(workgroups, std::move(corruptions), launch_workgroups);
+}
+
+// test hook: the raw fp32 buffer the smoke check reads, through the same code
+static py::bytes debug_mfma_smoke_dump(int device, int workgroups, int launch_workgroups) {
+  if (workgroups < 1 || workgroups > 4096)
+    throw py::value_error("workgroups must be in [1, 4096]");
+  use_device(device);
+  std::string raw;
+  (void)run_mfma_smoke(workgroups, {}, launch_workgroups, &raw);
+  return py::bytes(raw);
 }
 
 static double hbm_bandwidth_gb_s(int device, double gib, int iters) {
-  HIP_CHECK(hipSetDevice(device));
+  use_device(device);
   size_t bytes = (size_t)(gib * 1024.0 * 1024.0 * 1024.0);
   if (bytes < (64u << 20)) bytes = (64u << 20);
   return run_hbm_stream(bytes, iters);
@@ -710,7 +755,7 @@ static double hbm_bandwidth_gb_s(int device, double gib, int iters) {
 
 static py::dict health_check(int device, double hbm_floor_gb_s, bool quick) {
   py::dict result;
-  HIP_CHECK(hipSetDevice(device));
+  use_device(device);
   bool mfma_ok = run_mfma_smoke(quick ? 256 : 2048);
   // quick: 0.5 GiB per buffer (still > L2, probes real HBM); full: 4 GiB
   // (> 256 MiB L3 several times over per pass).
@@ -761,7 +806,7 @@ static py::dict hbm_pattern_check(int device, double mib, double fraction,
   if (corrupt_bit < 0 || corrupt_bit > 31) throw py::value_error("corrupt_bit must be in [0, 31]");
   if (corrupt_word < -1) throw py::value_error("corrupt_word is outside the swept range");
   if (corrupt_word >= 0) corruptions.emplace_back(corrupt_word, (int64_t)1 << corrupt_bit);
-  HIP_CHECK(hipSetDevice(device));
+  use_device(device);
   return pattern_dict(run_hbm_pattern(bytes, fraction, seed, passes, max_chunk_mib << 20,
                                       base_word, std::move(corruptions),
                                       corrupt_at.first, corrupt_at.second));
@@ -769,12 +814,12 @@ static py::dict hbm_pattern_check(int device, double mib, double fraction,
 
 static py::bytes debug_pattern_fill(int device, uint64_t bytes, uint32_t seed,
                                     bool invert, uint64_t base_word) {
-  HIP_CHECK(hipSetDevice(device));
+  use_device(device);
   return py::bytes(run_debug_pattern_fill(bytes, seed, invert, base_word));
 }
 
 static py::dict debug_stream_copy_check(int device, uint64_t bytes, uint32_t seed) {
-  HIP_CHECK(hipSetDevice(device));
+  use_device(device);
   const StreamCopyResult r = run_debug_stream_copy(bytes, seed);
   py::dict d = pattern_dict(r.pattern);
   d["guard_intact"] = r.guard_intact;
@@ -802,14 +847,14 @@ static py::dict mfma_verify(int device, const std::string& dtype, int workgroups
   const int dt = parse_dtype(dtype);
   if (corrupt_element < -1) throw py::value_error("corrupt_element is outside the output buffer");
   if (corrupt_element >= 0) corruptions.emplace_back(corrupt_element, (int64_t)1 << 20);
-  HIP_CHECK(hipSetDevice(device));
+  use_device(device);
   return mfma_dict(run_mfma_verify(dt, workgroups, seed, std::move(corruptions)));
 }
 
 static py::bytes debug_mfma_dump(int device, const std::string& dtype, int workgroups,
                                  uint32_t seed) {
   const int dt = parse_dtype(dtype);
-  HIP_CHECK(hipSetDevice(device));
+  use_device(device);
   return py::bytes(run_debug_mfma_dump(dt, workgroups, seed));
 }
 
@@ -828,7 +873,7 @@ static py::tuple mfma_verify_tile(int device, const std::string& dtype,
     }
     for (uint32_t c = 0; c < 16; ++c) C[i][c] = (float)gh::gen_c(seed, workgroup, dt, i, c);
   }
-  HIP_CHECK(hipSetDevice(device));
+  use_device(device);
   DeviceScope scope;
   float* d_out = (float*)scope.alloc(256 * sizeof(float));
   launch_mfma_exact(dt, d_out, 1, seed, workgroup);
@@ -908,7 +953,10 @@ PYBIND11_MODULE(gpuhealth, m) {
   m.def("device_count", &device_count);
   m.def("device_info", &device_info, py::arg("device") = 0);
   m.def("mfma_smoke", &mfma_smoke, py::arg("device") = 0,
-        py::arg("workgroups") = 2048);
+        py::arg("workgroups") = 2048, py::arg("corruptions") = corruptions_t{},
+        py::arg("launch_workgroups") = -1);
+  m.def("debug_mfma_smoke_dump", &debug_mfma_smoke_dump, py::arg("device") = 0,
+        py::arg("workgroups") = 64, py::arg("launch_workgroups") = -1);
   m.def("hbm_bandwidth_gb_s", &hbm_bandwidth_gb_s, py::arg("device") = 0,
         py::arg("gib") = 1.0, py::arg("iters") = 10);
   m.def("health_check", &health_check, py::arg("device") = 0,

@@ -55,33 +55,56 @@ class HealthReport:
     hbm_flipped_bits: Optional[int] = None
 
 
+def _rocm_smi_ok() -> bool:
+    try:
+        return bool(rocm_smi.get_gpu_stats())
+    except Exception:
+        return False
+
+
+def _gate_problems(result, hbm_floor_gb_s: float) -> list:
+    """What the quick/full gate found wrong, one entry per failed check."""
+    problems = []
+    if not result["mfma_ok"]:
+        problems.append("mfma_ok=False")
+    if not result["hbm_ok"]:
+        problems.append(f"hbm_gb_s={result['hbm_gb_s']:.0f} below the floor "
+                        f"of {hbm_floor_gb_s:.0f}")
+    return problems
+
+
+def _hip_failure(error: RuntimeError, rocm_ok: bool) -> HealthReport:
+    """A failing HIP call is the likeliest symptom of a wedged device: it is
+    the gate's verdict, not a crash of the probe."""
+    return HealthReport(healthy=False, rocm_smi_ok=rocm_ok, detail=str(error))
+
+
 def check_gpu_health(device: int = 0, quick: bool = False,
                      hbm_floor_gb_s: float = DEFAULT_HBM_FLOOR_GB_S) -> HealthReport:
     """Full gate: rocm-smi responds AND the device executes MFMA AND streams
-    HBM above the floor. Raises GpuHealthError on non-GPU hosts."""
+    HBM above the floor. Raises GpuHealthError on non-GPU hosts; ``detail``
+    names what failed, a HIP error of the device included."""
     if not gpu_node():
         raise GpuHealthError("not a GPU node (/dev/kfd missing)")
 
-    rocm_ok = True
-    try:
-        stats = rocm_smi.get_gpu_stats()
-        if not stats:
-            rocm_ok = False
-    except Exception:
-        rocm_ok = False
-
+    rocm_ok = _rocm_smi_ok()
     native = _load_native()
     if native.device_count() <= device:
         return HealthReport(healthy=False, rocm_smi_ok=rocm_ok,
                             detail=f"device {device} not visible to HIP")
-    result = native.health_check(device, hbm_floor_gb_s, quick)
+    try:
+        result = native.health_check(device, hbm_floor_gb_s, quick)
+    except RuntimeError as e:
+        return _hip_failure(e, rocm_ok)
+    problems = _gate_problems(result, hbm_floor_gb_s)
+    if not rocm_ok:
+        problems.append("rocm-smi did not respond")
     return HealthReport(
         healthy=bool(result["healthy"]) and rocm_ok,
         mfma_ok=bool(result["mfma_ok"]),
         hbm_gb_s=float(result["hbm_gb_s"]),
         rocm_smi_ok=rocm_ok,
-        detail="" if result["healthy"] else
-        f"mfma_ok={result['mfma_ok']} hbm_gb_s={result['hbm_gb_s']:.0f}",
+        detail="; ".join(problems),
     )
 
 
@@ -100,25 +123,19 @@ def check_gpu_burn_in(device: int = 0,
     if not 0.0 < hbm_fraction <= 1.0:
         raise ValueError(f"hbm_fraction must be in (0, 1], got {hbm_fraction}")
 
-    rocm_ok = True
-    try:
-        if not rocm_smi.get_gpu_stats():
-            rocm_ok = False
-    except Exception:
-        rocm_ok = False
-
+    rocm_ok = _rocm_smi_ok()
     native = _load_native()
     if native.device_count() <= device:
         return HealthReport(healthy=False, rocm_smi_ok=rocm_ok,
                             detail=f"device {device} not visible to HIP")
-    result = native.burn_in(device, hbm_fraction, hbm_floor_gb_s)
+    try:
+        result = native.burn_in(device, hbm_fraction, hbm_floor_gb_s)
+    except RuntimeError as e:
+        return _hip_failure(e, rocm_ok)
     pattern = result["hbm_pattern"]
     exact = {k: bool(v) for k, v in result["mfma_exact"].items()}
 
-    problems = []
-    if not result["mfma_ok"] or not result["hbm_ok"]:
-        problems.append(f"mfma_ok={result['mfma_ok']} "
-                        f"hbm_gb_s={result['hbm_gb_s']:.0f}")
+    problems = _gate_problems(result, hbm_floor_gb_s)
     for dtype, ok in exact.items():
         if not ok:
             wg, row, col, got, expected = result["mfma_first_bad"][dtype]
@@ -147,8 +164,9 @@ def check_gpu_burn_in(device: int = 0,
 
 def sim_kubelet_gpu_gate(pod: dict) -> bool:
     """gpu_gate hook for SimKubelet: a GPU-requesting pod only turns Ready if
-    the local MI355X passes the quick health gate."""
+    the local MI355X passes the quick health gate. Whatever the check raises
+    is a failed gate: a pod must never turn Ready because the probe crashed."""
     try:
         return check_gpu_health(quick=True).healthy
-    except GpuHealthError:
+    except Exception:
         return False

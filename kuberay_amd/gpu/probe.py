@@ -70,6 +70,8 @@ def main(argv=None) -> int:
     else:
         print(f"healthy={report.healthy} mfma_ok={report.mfma_ok} "
               f"hbm_gb_s={report.hbm_gb_s} rocm_smi_ok={report.rocm_smi_ok}")
+        if report.detail:
+            print(report.detail, file=sys.stderr)
     return 0 if report.healthy else 1
 
 

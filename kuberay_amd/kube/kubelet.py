@@ -166,7 +166,7 @@ class SimKubelet:
         pod = self.server.try_get("Pod", namespace, name)
         if pod is None or pod["metadata"].get("deletionTimestamp"):
             return
-        if self._requests_gpu(pod) and not self.gpu_gate(pod):
+        if self._requests_gpu(pod) and not self._gate_passes(pod):
             # GPU unhealthy: pod stays Pending (readiness probe failing)
             self.server.patch_merge("Pod", namespace, name, {
                 "status": {"phase": "Pending",
@@ -176,6 +176,14 @@ class SimKubelet:
         self.server.patch_merge("Pod", namespace, name,
                                 {"status": self._running_status(pod)},
                                 subresource="status")
+
+    def _gate_passes(self, pod: dict) -> bool:
+        # a gate that raises has not passed: without this the timer loop
+        # swallows the exception and the pod is left with no status at all
+        try:
+            return bool(self.gpu_gate(pod))
+        except Exception:
+            return False
 
     @staticmethod
     def _requests_gpu(pod: dict) -> bool:
