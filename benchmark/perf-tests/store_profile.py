@@ -1,8 +1,10 @@
 #!/usr/bin/env python3
-"""Where the control plane's CPU goes in the object store, per call site.
+"""Where the control plane's CPU goes, per call site: the object store, and
+above it the model copies, the typed gets by kind and the RayCluster
+reconciler's steps.
 
 Runs N bench-style steps (bench.py's run_step: create the RayClusters, wait
-for Ready, delete, drain) with the store's entry points and its JSON calls
+for Ready, delete, drain) with those entry points and the store's JSON calls
 wrapped in ``time.thread_time()`` and prints each site's share of the
 process CPU. The benchmark is one GIL-bound core of host work (the GPU idles
 during it), so this table — not a kernel profile — is what says where a
@@ -123,6 +125,41 @@ def instrument(sites: Sites) -> None:
     server_cls._notify = sites.wrap("InMemoryApiServer._notify", notify_flagged)
 
 
+RECONCILER_SITES = ("reconcile", "_create_head_pod", "_create_worker_pod",
+                    "_calculate_and_update_status", "_reconcile_head_service",
+                    "_update_endpoints", "_update_head_info")
+
+
+def instrument_reconciler(sites: Sites) -> None:
+    """The call sites above the store: model copies, typed gets by kind and
+    the RayCluster reconciler's steps (inclusive times; reconcile contains
+    the others)."""
+    from kuberay_amd.kube import client as client_mod
+    from kuberay_amd.kube import objects as objects_mod
+    from kuberay_amd.ops import raycluster as rc_mod
+
+    objects_mod.K8sModel.clone = sites.wrap(
+        "K8sModel.clone", objects_mod.K8sModel.clone)
+
+    real_get = client_mod.InMemoryClient.get
+    clock = time.thread_time
+
+    def get(self, model, namespace, name):
+        t0 = clock()
+        try:
+            return real_get(self, model, namespace, name)
+        finally:
+            sites.add(f"client.get({getattr(model, '__name__', model)})",
+                      clock() - t0)
+    client_mod.InMemoryClient.get = get
+
+    cls = rc_mod.RayClusterReconciler
+    for name in RECONCILER_SITES:
+        fn = getattr(cls, name, None)
+        if fn is not None:
+            setattr(cls, name, sites.wrap(f"RayClusterReconciler.{name}", fn))
+
+
 def main() -> int:
     parser = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     parser.add_argument("--clusters", type=int, default=200)
@@ -144,6 +181,7 @@ def main() -> int:
 
     sites = Sites()
     instrument(sites)
+    instrument_reconciler(sites)
 
     cp = ControlPlane(kubelet_delay=0.0, workers=args.controller_workers,
                       record_events=False, requeue_seconds=3600,
@@ -163,6 +201,11 @@ def main() -> int:
         cpu, wall = time.process_time() - cpu0, time.perf_counter() - wall0
         stats = getattr(cp.server._backend, "stats", None)
         engine_stats = stats() if stats else None
+        try:
+            from kuberay_amd._native import engine
+            copy_stats = engine.copy_stats()
+        except (ImportError, AttributeError):
+            copy_stats = None
     finally:
         cp.stop()
 
@@ -192,6 +235,9 @@ def main() -> int:
         print()
         print("engine counters (whole run, warm-up included): "
               + ", ".join(f"{k}={v}" for k, v in engine_stats.items()))
+    if copy_stats:
+        print("tree copier (whole run, warm-up included): "
+              + ", ".join(f"{k}={v}" for k, v in copy_stats.items()))
     if args.json:
         print(json.dumps({
             "root": root, "wall_s": wall, "cpu_s": cpu,

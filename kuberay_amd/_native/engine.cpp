@@ -6,7 +6,8 @@
 // of them. This backend keeps every object as compact JSON in C++ heap with
 // label / kind / owner-uid indexes beside it, plus precomputed "pod views"
 // (the 9 fields the RayCluster reconciler actually reads per pod per
-// reconcile) so the hot loop never materializes a pod at all.
+// reconcile) so the hot loop never materializes a pod at all, and the same
+// for the head Service (its clusterIP and ports).
 //
 // The engine owns the encoding too: put_object / put_status walk the Python
 // dict tree once, write compact JSON straight into the sections the store
@@ -31,6 +32,7 @@
 #include <vector>
 
 #include "store_core.hpp"
+#include "tree_copy.hpp"
 
 namespace py = pybind11;
 using namespace kuberay_store;
@@ -50,7 +52,8 @@ struct Keys {
   PyObject *metadata, *status, *spec, *labels, *ownerReferences, *uid,
       *resourceVersion, *finalizers, *deletionTimestamp, *name, *ns, *phase,
       *podIP, *restartPolicy, *creationTimestamp, *conditions, *type,
-      *containers, *containerStatuses, *state, *terminated;
+      *containers, *containerStatuses, *state, *terminated, *clusterIP, *ports,
+      *port, *nodePort;
 };
 Keys K;
 
@@ -68,6 +71,8 @@ void init_keys() {
   K.containers = mk("containers");
   K.containerStatuses = mk("containerStatuses"); K.state = mk("state");
   K.terminated = mk("terminated");
+  K.clusterIP = mk("clusterIP"); K.ports = mk("ports"); K.port = mk("port");
+  K.nodePort = mk("nodePort");
 }
 
 // ---------------------------------------------------------------------------
@@ -322,6 +327,63 @@ void extract_view(PyObject* obj, PyObject* meta, PodViewData& v) {
   }
 }
 
+// compute_service_view (kube/store.py), field for field. False stands for its
+// None: the object has a shape the view does not describe, it gets no view,
+// and readers take the typed path for it.
+bool optional_port(PyObject* d, PyObject* key, int64_t& out, bool& has) {
+  PyObject* v = dget(d, key);
+  has = false;
+  if (v == nullptr || v == Py_None) return true;
+  if (!PyLong_CheckExact(v)) return false;  // bool, str, float, subclass
+  int overflow = 0;
+  const long long n = PyLong_AsLongLongAndOverflow(v, &overflow);
+  if (overflow) return false;
+  out = n;
+  has = true;
+  return true;
+}
+
+bool extract_service_view(PyObject* obj, PyObject* meta, ServiceViewData& v) {
+  try {
+    v.name = str_default(meta, K.name, "");
+    v.ns = str_default(meta, K.ns, "default");
+    PyObject* spec = dget(obj, K.spec);
+    if (spec == nullptr) return true;
+    if (!PyDict_CheckExact(spec)) return false;
+    PyObject* ip = dget(spec, K.clusterIP);
+    if (ip != nullptr && ip != Py_None) {
+      v.cluster_ip = to_utf8(ip);
+      if (v.cluster_ip.empty()) return false;  // "" and "no clusterIP" differ
+    }
+    PyObject* ports = dget(spec, K.ports);
+    if (ports == nullptr || ports == Py_None) return true;
+    if (!PyList_CheckExact(ports)) return false;
+    const Py_ssize_t n = PyList_GET_SIZE(ports);
+    v.ports.reserve(n);
+    for (Py_ssize_t i = 0; i < n; ++i) {
+      PyObject* port = PyList_GET_ITEM(ports, i);
+      if (!PyDict_CheckExact(port)) return false;
+      ServicePortView pv;
+      PyObject* name = dget(port, K.name);
+      if (name != nullptr && name != Py_None) pv.name = to_utf8(name);
+      if (!optional_port(port, K.port, pv.port, pv.has_port) ||
+          !optional_port(port, K.nodePort, pv.node_port, pv.has_node_port)) {
+        return false;
+      }
+      v.ports.push_back(std::move(pv));
+    }
+    return true;
+  } catch (const Decline&) {
+    return false;
+  }
+}
+
+// (name, namespace, clusterIP, [(name, port or None, nodePort or None)])
+using PortTuple =
+    std::tuple<std::string, std::optional<int64_t>, std::optional<int64_t>>;
+using ServiceViewTuple =
+    std::tuple<std::string, std::string, std::string, std::vector<PortTuple>>;
+
 Section make_section(const std::string& scratch) {
   return std::make_shared<const std::string>(scratch.data(), scratch.size());
 }
@@ -378,6 +440,8 @@ class NativeStore {
       if (kind == "Pod") {
         extract_view(o, meta, f.view);
         f.has_view = true;
+      } else if (kind == "Service") {
+        f.has_service_view = extract_service_view(o, meta, f.service_view);
       }
       blob.rest = make_section(rest);
       if (has_meta) blob.meta = make_section(meta_s);
@@ -439,7 +503,8 @@ class NativeStore {
            const std::optional<PodViewData>& view,
            const std::optional<std::string>& event_type,
            const std::string& uid, bool has_finalizers,
-           const std::string& deletion_ts) {
+           const std::string& deletion_ts,
+           const std::optional<ServiceViewTuple>& service_view) {
     Blob b;
     b.rest = std::make_shared<const std::string>(blob);
     b.whole = true;
@@ -448,6 +513,23 @@ class NativeStore {
     f.has_finalizers = has_finalizers;
     f.labels = labels; f.owner_uids = owner_uids;
     if (view) { f.has_view = true; f.view = *view; }
+    if (service_view) {
+      f.has_service_view = true;
+      ServiceViewData& sv = f.service_view;
+      sv.name = std::get<0>(*service_view);
+      sv.ns = std::get<1>(*service_view);
+      sv.cluster_ip = std::get<2>(*service_view);
+      for (const PortTuple& t : std::get<3>(*service_view)) {
+        ServicePortView pv;
+        pv.name = std::get<0>(t);
+        if (std::get<1>(t)) { pv.has_port = true; pv.port = *std::get<1>(t); }
+        if (std::get<2>(t)) {
+          pv.has_node_port = true;
+          pv.node_port = *std::get<2>(t);
+        }
+        sv.ports.push_back(std::move(pv));
+      }
+    }
     return core_.put(kind, ns, name, std::move(b), std::move(f),
                      event_type ? event_type->c_str() : nullptr);
   }
@@ -521,6 +603,20 @@ class NativeStore {
     return out;
   }
 
+  std::optional<ServiceViewTuple> service_view(const std::string& ns,
+                                               const std::string& name) const {
+    std::optional<ServiceViewData> v = core_.service_view(ns, name);
+    if (!v) return std::nullopt;
+    std::vector<PortTuple> ports;
+    ports.reserve(v->ports.size());
+    for (const ServicePortView& p : v->ports) {
+      ports.emplace_back(
+          p.name, p.has_port ? std::optional<int64_t>(p.port) : std::nullopt,
+          p.has_node_port ? std::optional<int64_t>(p.node_port) : std::nullopt);
+    }
+    return ServiceViewTuple(v->name, v->ns, v->cluster_ip, std::move(ports));
+  }
+
   std::vector<py::tuple> dependents(const std::string& uid) const {
     std::vector<py::tuple> out;
     for (const auto& t : core_.dependents(uid)) {
@@ -581,8 +677,29 @@ class NativeStore {
 
 PYBIND11_MODULE(engine, m) {
   m.doc() = "kuberay-amd native object store (C++ sections + indexes + pod "
-            "views + watch history, native JSON encoding)";
+            "and Service views + watch history, native JSON encoding) and "
+            "model-tree copier";
   init_keys();
+
+  // Deep copy of a pydantic model tree (tree_copy.hpp). copy_configure takes
+  // pydantic.BaseModel once, so the engine imports where pydantic is absent.
+  m.def("copy_configure", [](py::handle base_model) {
+    return kuberay_copy::configure(base_model.ptr());
+  }, py::arg("base_model"),
+        "Hand the copier pydantic.BaseModel; returns whether it is enabled.");
+  m.def("copy_tree", [](py::handle obj) -> py::object {
+    PyObject* out = kuberay_copy::copy_tree(obj.ptr());
+    if (out == nullptr) return py::none();
+    return py::reinterpret_steal<py::object>(out);
+  }, py::arg("obj"),
+        "copy.deepcopy of a model tree, or None when it declines.");
+  m.def("copy_stats", []() {
+    const kuberay_copy::State& s = kuberay_copy::state();
+    py::dict d;
+    d["copies"] = s.copies;
+    d["declines"] = s.declines;
+    return d;
+  });
 
   py::class_<PodViewData>(m, "PodViewData")
       .def(py::init<>())
@@ -608,7 +725,8 @@ PYBIND11_MODULE(engine, m) {
            py::arg("name"), py::arg("blob"), py::arg("rv"), py::arg("labels"),
            py::arg("owner_uids"), py::arg("view") = std::nullopt,
            py::arg("event_type") = std::nullopt, py::arg("uid") = "",
-           py::arg("has_finalizers") = false, py::arg("deletion_ts") = "")
+           py::arg("has_finalizers") = false, py::arg("deletion_ts") = "",
+           py::arg("service_view") = std::nullopt)
       .def("fetch", &NativeStore::fetch)
       .def("rv", &NativeStore::rv)
       .def("peek", &NativeStore::peek)
@@ -619,6 +737,7 @@ PYBIND11_MODULE(engine, m) {
            py::arg("ns") = std::nullopt, py::arg("selector") = LabelList())
       .def("list_views", &NativeStore::list_views, py::arg("ns") = std::nullopt,
            py::arg("selector") = LabelList())
+      .def("service_view", &NativeStore::service_view)
       .def("dependents", &NativeStore::dependents)
       .def("drop_owner", &NativeStore::drop_owner)
       .def("count", &NativeStore::count)

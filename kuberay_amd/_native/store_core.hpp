@@ -1,8 +1,8 @@
 // store_core — the Python-free half of the native object store.
 //
 // Everything here is plain C++17: entries, the kind / label / owner-uid
-// indexes, the three shared JSON sections of every object, the watch history
-// ring and the work counters. engine.cpp adds the pybind11 bindings and the
+// indexes, the pod and Service views, the three shared JSON sections of every
+// object, the watch history ring and the work counters. engine.cpp adds the pybind11 bindings and the
 // PyObject encoder on top; tests/native/store_core_check.cpp drives this
 // header alone (under sanitizers).
 //
@@ -43,6 +43,20 @@ struct PodViewData {
   std::string name, ns, phase, deletion_ts, pod_ip, restart_policy, creation_ts;
   bool ready = false;
   bool terminated = false;
+};
+
+// What the RayCluster reconciler reads from a Service: whether it exists,
+// its clusterIP ("" when it has none) and (name, port, nodePort) per port.
+// A port number the object does not carry has its flag false.
+struct ServicePortView {
+  std::string name;
+  int64_t port = 0, node_port = 0;
+  bool has_port = false, has_node_port = false;
+};
+
+struct ServiceViewData {
+  std::string name, ns, cluster_ip;
+  std::vector<ServicePortView> ports;
 };
 
 // The stored form of one object version.
@@ -102,6 +116,10 @@ struct Fields {
   std::vector<std::string> owner_uids;
   bool has_view = false;
   PodViewData view;
+  // Services only. A status write keeps it: everything in it comes from
+  // spec and from metadata a status write cannot change.
+  bool has_service_view = false;
+  ServiceViewData service_view;
 };
 
 struct Peek {
@@ -267,6 +285,18 @@ class StoreCore {
       out.push_back(ViewRow{e->f.view, e->f.labels});
     }
     return out;
+  }
+
+  // The view of Service ns/name; nullopt when there is no such Service or
+  // its last full write produced no view.
+  std::optional<ServiceViewData> service_view(const std::string& ns,
+                                              const std::string& name) const {
+    std::lock_guard<std::mutex> g(mu_);
+    auto it = objects_.find(make_key("Service", ns, name));
+    if (it == objects_.end() || !it->second.f.has_service_view) {
+      return std::nullopt;
+    }
+    return it->second.f.service_view;
   }
 
   std::vector<std::tuple<std::string, std::string, std::string>> dependents(

@@ -6,9 +6,7 @@ raycluster_controller.go:226-352).
 """
 from __future__ import annotations
 
-import copy
-
-from ..kube.objects import Job, JobSpec, ObjectMeta, PodTemplateSpec
+from ..kube.objects import Job, JobSpec, ObjectMeta, PodTemplateSpec, deep_copy
 from ..models.raycluster import RayCluster, RayNodeType
 from ..utils import constants as C
 from ..utils import names
@@ -40,7 +38,7 @@ def build_redis_cleanup_job(cluster: RayCluster) -> Job:
     container.liveness_probe = None
     container.readiness_probe = None
     container.lifecycle = None
-    container.resources = copy.deepcopy(container.resources)
+    container.resources = deep_copy(container.resources)
 
     opts = cluster.spec.gcs_fault_tolerance_options
     if opts:

@@ -24,7 +24,6 @@ these MI355X-native differences:
 """
 from __future__ import annotations
 
-import copy
 import json
 import os
 from typing import Dict, List, Optional
@@ -42,6 +41,7 @@ from ..kube.objects import (
     ResourceRequirements,
     Volume,
     VolumeMount,
+    deep_copy,
 )
 from ..models.raycluster import RayCluster, RayNodeType, WorkerGroupSpec
 from ..utils import constants as C
@@ -635,9 +635,9 @@ def default_worker_pod_template(cluster: RayCluster, worker_spec: WorkerGroupSpe
             image_pull_policy=ray_container.image_pull_policy,
             command=["/bin/bash", "-lc", "--"],
             args=[wait_script],
-            security_context=copy.deepcopy(ray_container.security_context),
-            env=copy.deepcopy(ray_container.env),
-            volume_mounts=copy.deepcopy(ray_container.volume_mounts),
+            security_context=deep_copy(ray_container.security_context),
+            env=deep_copy(ray_container.env),
+            volume_mounts=deep_copy(ray_container.volume_mounts),
             resources=ResourceRequirements(
                 limits={"cpu": "200m", "memory": "256Mi"},
                 requests={"cpu": "200m", "memory": "256Mi"},

@@ -214,6 +214,11 @@ class InMemoryClient(KubeClient):
         """Reconcile hot-loop projection (no pod materialization)."""
         return self.server.list_pod_views(namespace, label_selector)
 
+    def service_view(self, namespace, name):
+        """Projection of a stored Service (kube/store.py ServiceView); None
+        when there is none to be had and the caller must get the object."""
+        return self.server.service_view(namespace, name)
+
     def delete(self, model_or_obj, namespace=None, name=None):
         if namespace is None:
             namespace = model_or_obj.metadata.namespace or "default"

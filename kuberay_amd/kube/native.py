@@ -5,7 +5,8 @@ The engine owns the encoding: a write hands it the dict tree and it encodes,
 indexes, computes the pod view and records the watch-history entry in one
 call; a status write re-encodes metadata + status only. Objects live in the
 C++ heap as shared JSON sections; reads parse on demand; the reconcile hot
-loop reads precomputed pod views without touching any JSON at all.
+loop reads precomputed pod and Service views without touching any JSON at
+all.
 
 Trees the native encoder declines (tuples, subclasses, non-str keys, big
 ints, NaN/Inf, lone surrogates, very deep nesting) take the json.dumps +
@@ -18,7 +19,7 @@ import os
 from typing import Any, Dict, List, Optional, Tuple
 
 from .._native import engine  # raises ImportError if not built
-from .store import Key, PodView
+from .store import Key, PodView, ServiceView, compute_service_view
 
 _dumps = json.dumps
 _loads = json.loads
@@ -86,6 +87,11 @@ class NativeBackend:
         owners = [ref.get("uid") for ref in meta.get("ownerReferences") or []
                   if ref.get("uid")]
         view = _view_of(obj) if kind == "Pod" else None
+        service_view = None
+        if kind == "Service":
+            sv = compute_service_view(obj)
+            if sv is not None:
+                service_view = (sv.name, sv.namespace, sv.cluster_ip, sv.ports)
         blob = _dumps(obj, separators=(",", ":"))
         uid = meta.get("uid")
         deletion_ts = meta.get("deletionTimestamp") or ""
@@ -94,7 +100,7 @@ class NativeBackend:
         return self._store.put(
             kind, ns, name, blob, meta.get("resourceVersion", ""), labels,
             owners, view, event_type, uid if isinstance(uid, str) else "",
-            bool(meta.get("finalizers")), deletion_ts)
+            bool(meta.get("finalizers")), deletion_ts, service_view)
 
     def put_status(self, key: Key, obj: Dict[str, Any],
                    event_type: Optional[str] = None) -> None:
@@ -149,6 +155,15 @@ class NativeBackend:
                     creation_timestamp=r[9])
             for r in rows
         ]
+
+    def service_view(self, key: Key) -> Optional[ServiceView]:
+        """The view the engine computed when the Service was last written in
+        full; None when missing or when that write produced no view."""
+        row = self._store.service_view(key[1], key[2])
+        if row is None:
+            return None
+        return ServiceView(name=row[0], namespace=row[1], cluster_ip=row[2],
+                           ports=row[3])
 
     def dependents(self, uid: str) -> List[Key]:
         return [tuple(t) for t in self._store.dependents(uid)]

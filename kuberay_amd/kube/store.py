@@ -129,6 +129,73 @@ def compute_pod_view(obj: Dict[str, Any]) -> PodView:
 
 
 # ---------------------------------------------------------------------------
+# service views — what the RayCluster reconciler reads from the head Service
+# ---------------------------------------------------------------------------
+
+@dataclasses.dataclass
+class ServiceView:
+    name: str
+    namespace: str
+    cluster_ip: str = ""  # "" when the Service has none
+    # (name or "", port or None, nodePort or None) per port
+    ports: List[Tuple[str, Optional[int], Optional[int]]] = dataclasses.field(
+        default_factory=list)
+
+
+_INT64 = 1 << 63
+
+
+def _view_port_number(value):
+    """None or an exact int64 passes; anything else (bool, str, float,
+    subclass) has no place in a view."""
+    if value is None:
+        return True
+    return type(value) is int and -_INT64 <= value < _INT64
+
+
+def compute_service_view(obj: Dict[str, Any]) -> Optional[ServiceView]:
+    """The view of a stored Service, or None when the object has a shape the
+    view does not describe exactly; readers then take the typed path, so a
+    view is never wrong. The engine computes the same from the tree it
+    encodes (extract_service_view in _native/engine.cpp)."""
+    meta = obj.get("metadata", {})
+    if type(meta) is not dict:
+        return None
+    name = meta.get("name", "")
+    namespace = meta.get("namespace", "default")
+    if type(name) is not str or type(namespace) is not str:
+        return None
+    view = ServiceView(name=name, namespace=namespace)
+    if "spec" not in obj:
+        return view
+    spec = obj["spec"]
+    if type(spec) is not dict:
+        return None
+    ip = spec.get("clusterIP")
+    if ip is not None:
+        if type(ip) is not str or not ip:
+            return None  # "" and "no clusterIP" differ
+        view.cluster_ip = ip
+    ports = spec.get("ports")
+    if ports is None:
+        return view
+    if type(ports) is not list:
+        return None
+    for port in ports:
+        if type(port) is not dict:
+            return None
+        pname = port.get("name")
+        if pname is None:
+            pname = ""
+        number, node_port = port.get("port"), port.get("nodePort")
+        if (type(pname) is not str or not _view_port_number(number)
+                or not _view_port_number(node_port)):
+            return None
+        view.ports.append((pname, number, node_port))
+    return view
+
+
+# ---------------------------------------------------------------------------
 # storage backends
 # ---------------------------------------------------------------------------
 
@@ -141,6 +208,7 @@ class PyBackend:
     def __init__(self) -> None:
         self._objects: Dict[Key, Dict[str, Any]] = {}
         self._views: Dict[Key, PodView] = {}
+        self._service_views: Dict[Key, ServiceView] = {}
         self._label_index: Dict[Tuple[str, str, str], set] = defaultdict(set)
         self._kind_index: Dict[str, set] = defaultdict(set)
         self._owner_index: Dict[str, set] = defaultdict(set)
@@ -154,6 +222,12 @@ class PyBackend:
         self._index_add(key, stored)
         if key[0] == "Pod":
             self._views[key] = compute_pod_view(stored)
+        elif key[0] == "Service":
+            view = compute_service_view(stored)
+            if view is not None:
+                self._service_views[key] = view
+            else:
+                self._service_views.pop(key, None)
 
     def fetch(self, key: Key) -> Optional[Dict[str, Any]]:
         obj = self._objects.get(key)
@@ -174,7 +248,11 @@ class PyBackend:
         if obj is not None:
             self._index_remove(key, obj)
             self._views.pop(key, None)
+            self._service_views.pop(key, None)
         return obj
+
+    def service_view(self, key: Key) -> Optional[ServiceView]:
+        return self._service_views.get(key)
 
     def _select_keys(self, kind: str, namespace: Optional[str],
                      selector: Optional[Dict[str, str]]) -> List[Key]:
@@ -411,6 +489,16 @@ class InMemoryApiServer:
         """Reconcile-hot-loop projection (no pod materialization)."""
         with self._lock:
             return self._backend.list_views(namespace, label_selector)
+
+    def service_view(self, namespace: str, name: str) -> Optional[ServiceView]:
+        """The stored Service's view, or None when there is no such Service,
+        it has no view, or the backend keeps none: callers then read the
+        object itself."""
+        fn = getattr(self._backend, "service_view", None)
+        if fn is None:
+            return None
+        with self._lock:
+            return fn(("Service", namespace, name))
 
     def update(self, obj: Dict[str, Any], *, subresource: Optional[str] = None,
                assume_owned: bool = False) -> Dict[str, Any]:

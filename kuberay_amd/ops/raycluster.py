@@ -165,6 +165,11 @@ class RayClusterReconcilerOptions:
 
 
 class RayClusterReconciler(Reconciler):
+    # Measurement switches, read once: with one off, that part takes the path
+    # it replaced. Results are the same either way.
+    group_pod_reuse = os.environ.get("KUBERAY_GROUP_POD_REUSE", "1") != "0"
+    service_views = os.environ.get("KUBERAY_SERVICE_VIEW", "1") != "0"
+
     def __init__(self, client: KubeClient, recorder: Optional[EventRecorder] = None,
                  expectations=None, batch_scheduler=None,
                  options: Optional[RayClusterReconcilerOptions] = None,
@@ -384,7 +389,23 @@ class RayClusterReconciler(Reconciler):
             )
             self._create_if_absent(secret, cluster)
 
+    def _head_service_view(self, cluster: RayCluster):
+        """The head Service's view (kube/store.py ServiceView) from clients
+        that keep one; None when the client has no views, the Service has
+        none or does not exist, and the caller reads the typed object."""
+        if not self.service_views:
+            return None
+        service_view = getattr(self.client, "service_view", None)
+        if service_view is None:
+            return None
+        return service_view(
+            cluster.metadata.namespace or "default",
+            names.head_service_name(C.KIND_RAYCLUSTER, cluster.spec,
+                                    cluster.metadata.name))
+
     def _reconcile_head_service(self, cluster: RayCluster) -> None:
+        if self._head_service_view(cluster) is not None:
+            return  # it exists; nothing is ever done to an existing one
         svc = servicelib.build_head_service(cluster)
         self._create_if_absent(svc, cluster)
 
@@ -599,8 +620,18 @@ class RayClusterReconciler(Reconciler):
         desired = res.worker_group_desired_replicas(group)
         diff = desired - len(running)
         if diff > 0:
+            # The pods of one scale-up differ only in their replica-index
+            # label (name, uid and resourceVersion come from the store), so
+            # the first is built and the others are copies of it. Nothing is
+            # kept beyond this call.
+            prototype = None
             for i in range(diff):
-                self._create_worker_pod(cluster, group, replica_index=len(running) + i)
+                kept = self._create_worker_pod(
+                    cluster, group, replica_index=len(running) + i,
+                    prototype=prototype,
+                    keep_prototype=(self.group_pod_reuse and prototype is None
+                                    and i + 1 < diff))
+                prototype = prototype or kept
         elif diff < 0:
             # scale down without explicit WorkersToDelete: random deletion is
             # gated when autoscaling is enabled (controller.go:1222-1256)
@@ -700,7 +731,38 @@ class RayClusterReconciler(Reconciler):
 
     def _create_worker_pod(self, cluster: RayCluster, group: WorkerGroupSpec,
                            replica_index: int = 0, host_index: int = 0,
-                           replica_grp_name: Optional[str] = None) -> None:
+                           replica_grp_name: Optional[str] = None,
+                           prototype: Optional[k8s.Pod] = None,
+                           keep_prototype: bool = False) -> Optional[k8s.Pod]:
+        """Create one worker pod: built from the group spec, or, given the
+        ``prototype`` an earlier call of the same scale-up returned, a copy
+        of it with this replica's index. With ``keep_prototype`` the pod is
+        returned as built, before a batch scheduler edits it."""
+        namespace = cluster.metadata.namespace or "default"
+        if prototype is None:
+            pod = self._build_worker_pod(cluster, group, replica_index,
+                                         host_index, replica_grp_name)
+        else:
+            pod = prototype.clone()
+            pod.metadata.labels[C.RAY_WORKER_REPLICA_INDEX_KEY] = str(replica_index)
+        kept = None
+        if keep_prototype:
+            kept = pod.clone() if self.batch_scheduler is not None else pod
+        if self.batch_scheduler is not None:
+            self.batch_scheduler.add_metadata_to_pod(self.client, cluster,
+                                                     group.group_name, pod)
+        created = self.client.create(pod)
+        self.expectations.expect_create_pod(namespace, cluster.metadata.name,
+                                            group.group_name, created.metadata.name)
+        self.recorder.eventf(cluster, "Normal", "CreatedWorkerPod",
+                             "Created worker Pod %s", created.metadata.name)
+        return kept
+
+    def _build_worker_pod(self, cluster: RayCluster, group: WorkerGroupSpec,
+                          replica_index: int = 0, host_index: int = 0,
+                          replica_grp_name: Optional[str] = None) -> k8s.Pod:
+        """default_worker_pod_template → sidecars → build_pod → owner
+        reference → hash label."""
         namespace = cluster.metadata.namespace or "default"
         pod_name = names.pod_name(
             names.check_name(f"{cluster.metadata.name}-{group.group_name}"),
@@ -723,14 +785,8 @@ class RayClusterReconciler(Reconciler):
         pod.metadata.owner_references = [k8s.owner_reference_for(cluster)]
         pod.metadata.labels[C.HASH_WITHOUT_REPLICAS_AND_WORKERS_TO_DELETE_KEY] = \
             self._spec_hash(cluster)
-        if self.batch_scheduler is not None:
-            self.batch_scheduler.add_metadata_to_pod(self.client, cluster,
-                                                     group.group_name, pod)
-        created = self.client.create(pod)
-        self.expectations.expect_create_pod(namespace, cluster.metadata.name,
-                                            group.group_name, created.metadata.name)
-        self.recorder.eventf(cluster, "Normal", "CreatedWorkerPod",
-                             "Created worker Pod %s", created.metadata.name)
+        return pod
+
 
     # ------------------------------------------------------------------
     # status
@@ -849,6 +905,12 @@ class RayClusterReconciler(Reconciler):
     def _update_endpoints(self, cluster: RayCluster) -> None:
         svc_name = names.head_service_name(C.KIND_RAYCLUSTER, cluster.spec,
                                            cluster.metadata.name)
+        view = self._head_service_view(cluster)
+        if view is not None:
+            cluster.status.endpoints = {
+                pname: str(node_port or port)
+                for pname, port, node_port in view.ports if pname}
+            return
         svc = self.client.try_get(k8s.Service, cluster.metadata.namespace or "default",
                                   svc_name)
         if svc is None:
@@ -869,6 +931,12 @@ class RayClusterReconciler(Reconciler):
             info.pod_ip = None
         svc_name = names.head_service_name(C.KIND_RAYCLUSTER, cluster.spec,
                                            cluster.metadata.name)
+        view = self._head_service_view(cluster)
+        if view is not None:
+            info.service_name = view.name
+            info.service_ip = ((view.cluster_ip or None)
+                               if view.cluster_ip != "None" else info.pod_ip)
+            return
         svc = self.client.try_get(k8s.Service, cluster.metadata.namespace or "default",
                                   svc_name)
         if svc is not None:
