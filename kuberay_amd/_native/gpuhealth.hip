@@ -46,6 +46,27 @@
 //                    in [-8, 8], so the low mantissa bits of bf16 (4..0), f16
 //                    (7..0) and fp8 (0) are 0 in every operand: a stuck-at-0
 //                    fault there is outside what this data can show.
+//   * cu_sweep     — workgroups of four waves that each take the whole LDS of
+//                    a CU (the device's maximum per block, so one workgroup
+//                    owns its CU), read where they run (XCC_ID and HW_ID
+//                    registers: XCC, SE, SH, CU, and the SIMD of each wave),
+//                    march the pattern over all of that LDS (16-byte fill;
+//                    verified with 16-byte reads and again with dword reads
+//                    on a rotated lane map; plain and inverted) and run the
+//                    four exact MFMA tiles on each wave's SIMD. Results go to
+//                    a table with one slot per CU. Rounds are launched until
+//                    as many CUs were visited as the device has, or a limit.
+//                    Proves, for every CU it reports as covered: each LDS
+//                    word held both values of each bit, and each of the four
+//                    matrix pipes gave exact products; a fault is named by
+//                    XCC/SE/SH/CU (and SIMD, data type). Cannot show: a CU
+//                    the dispatcher never gave us (reported as incomplete
+//                    coverage, fatal only on request), LDS faults that need
+//                    another access pattern (ds_read_b64, transposed reads,
+//                    neighbouring-cell coupling), and which CU is missing —
+//                    only covered places are known. No workgroup waits on
+//                    another. Test hooks: cu_sweep(inject_lds=, inject_mfma=)
+//                    and debug_cu_lds_dump (the fill's LDS, copied out).
 //
 // What must agree between host and device (pattern, generators, encoders,
 // reference) is in gpuhealth_ref.hpp.
@@ -60,8 +81,10 @@
 
 #include <algorithm>
 #include <cstdint>
+#include <optional>
 #include <stdexcept>
 #include <string>
+#include <tuple>
 #include <utility>
 #include <vector>
 
@@ -714,6 +737,356 @@ static std::string run_debug_mfma_dump(int dtype, int workgroups, uint32_t seed)
 }
 
 // ---------------------------------------------------------------------------
+// Burn-in, part 3: CU sweep — LDS march and exact MFMA per SIMD, with the
+// place each workgroup ran on
+//
+// A workgroup of four waves takes lds_bytes of dynamic LDS; at the device's
+// maximum it owns its CU. It never waits on another workgroup: coverage comes
+// from launching more of them (run_cu_sweep), never from holding CUs.
+// ---------------------------------------------------------------------------
+constexpr int kSweepThreads = 256;
+constexpr int kSweepWaves = kSweepThreads / 64;
+// dword verify: lane-to-address map rotated against the fill's, by a
+// non-multiple of 64 words so that each bank is read from another lane
+constexpr uint32_t kLdsVerifyRotation = 17;
+
+struct LdsStats {
+  unsigned long long bad_words;
+  unsigned long long flipped_bits;
+  unsigned long long first_bad_word;  // LDS word index, ~0 when clean
+  unsigned int bad_bit_mask;          // OR of every XOR difference
+  unsigned int reserved;
+};
+
+struct CuSlot {
+  unsigned int visits;
+  unsigned int simd_seen;  // bit s: a wave of some visit ran on SIMD s
+  LdsStats lds;
+  unsigned int mfma_bad[gh::kNumSimds][gh::kNumDtypes];
+};
+
+// what one workgroup saw, at records[visit]; lds is per wave (plain stores,
+// the host adds them up)
+struct CuRecord {
+  unsigned int written;  // 1 once wave 0 has been here
+  unsigned int key;
+  unsigned int xcc_id_reg, hw_id_reg;  // raw, as wave 0 read them
+  unsigned int simd[kSweepWaves];
+  LdsStats lds[kSweepWaves];
+};
+
+// test hook, applied by the kernel itself to the one visit it names
+struct CuInject {
+  uint32_t lds_on = 0, lds_visit = 0, lds_word = 0, lds_mask = 0, lds_phase = 0;
+  uint32_t mfma_on = 0, mfma_visit = 0, mfma_wave = 0, mfma_dtype = 0,
+           mfma_element = 0, mfma_mask = 0;
+};
+
+__device__ inline uint32_t read_xcc_id_reg() {
+  uint32_t v;
+  asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(v));
+  return v;
+}
+__device__ inline uint32_t read_hw_id_reg() {
+  uint32_t v;
+  asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(v));
+  return v;
+}
+
+__device__ inline uint4 lds_pattern_vec(uint32_t seed, uint32_t visit, uint32_t vec,
+                                        uint32_t invert_mask) {
+  uint4 v;
+  v.x = gh::pattern_word(seed, gh::lds_pattern_index(visit, 4 * vec)) ^ invert_mask;
+  v.y = gh::pattern_word(seed, gh::lds_pattern_index(visit, 4 * vec + 1)) ^ invert_mask;
+  v.z = gh::pattern_word(seed, gh::lds_pattern_index(visit, 4 * vec + 2)) ^ invert_mask;
+  v.w = gh::pattern_word(seed, gh::lds_pattern_index(visit, 4 * vec + 3)) ^ invert_mask;
+  return v;
+}
+
+// the one fill of the march: 16-byte vectors, thread t takes t, t + 256, ...
+__device__ inline void lds_fill(uint4* lds, uint32_t n_vec, uint32_t seed,
+                                uint32_t visit, uint32_t invert_mask) {
+  for (uint32_t v = threadIdx.x; v < n_vec; v += kSweepThreads)
+    lds[v] = lds_pattern_vec(seed, visit, v, invert_mask);
+}
+
+struct LaneStats {
+  unsigned long long bad = 0, bits = 0, first = kNoBadWord;
+  unsigned int mask = 0;
+  __device__ inline void see(uint32_t diff, uint32_t word) {
+    if (diff != 0) {
+      ++bad;
+      bits += __popc(diff);
+      mask |= diff;
+      if (word < first) first = word;
+    }
+  }
+};
+
+// one exact tile on this wave's matrix pipe; returns this lane's bad D registers
+template <int DT>
+__device__ inline unsigned int sweep_mfma_bad(uint32_t seed, uint32_t wg, int lane,
+                                              bool inject, uint32_t inj_element,
+                                              uint32_t inj_mask) {
+  const uint32_t col = lane & 15, row0 = 4 * (lane >> 4);
+  frag_cd_t acc;
+  for (uint32_t r = 0; r < 4; ++r) acc[r] = (float)gh::gen_c(seed, wg, DT, row0 + r, col);
+  acc = mfma_exact_tile<DT>(seed, wg, lane, acc);
+  unsigned int bad = 0;
+  for (uint32_t r = 0; r < 4; ++r) {
+    float got = acc[r];
+    if (inject && inj_element == (row0 + r) * 16 + col)
+      got = gh::bits_f32(gh::f32_bits(got) ^ inj_mask);
+    if (!(got == gh::reference_element(DT, seed, wg, row0 + r, col))) ++bad;
+  }
+  return bad;
+}
+
+__global__ __launch_bounds__(kSweepThreads) void cu_sweep_kernel(
+    CuSlot* __restrict__ slots, CuRecord* __restrict__ records, uint32_t visit_base,
+    uint32_t seed, int passes, uint32_t lds_bytes, CuInject inj) {
+  extern __shared__ uint4 lds_vec[];
+  const uint32_t* lds_words = (const uint32_t*)lds_vec;
+  const uint32_t visit = visit_base + blockIdx.x;
+  const int lane = threadIdx.x & 63;
+  const uint32_t wave = threadIdx.x >> 6;
+  const uint32_t n_vec = lds_bytes / 16, n_words = lds_bytes / 4;
+
+  // 1. locate: every wave reads its own registers
+  const uint32_t xcc_reg = read_xcc_id_reg(), hw_reg = read_hw_id_reg();
+  const gh::CuLocation loc = gh::decode_location(xcc_reg, hw_reg);
+  const uint32_t key = gh::location_key(loc);
+  CuSlot* slot = slots + key;
+  CuRecord* rec = records + visit;
+
+  // 2. LDS march
+  LaneStats st;
+  const uint32_t rot = kLdsVerifyRotation % n_words;
+  for (int pass = 0; pass < passes; ++pass) {
+    for (uint32_t phase = 0; phase < 2; ++phase) {
+      const uint32_t inv = phase ? 0xFFFFFFFFu : 0u;
+      __syncthreads();  // the previous phase's reads are done
+      lds_fill(lds_vec, n_vec, seed, visit, inv);
+      __syncthreads();
+      if (inj.lds_on && visit == inj.lds_visit && phase == inj.lds_phase && pass == 0) {
+        if (threadIdx.x == 0) ((uint32_t*)lds_vec)[inj.lds_word] ^= inj.lds_mask;
+        __syncthreads();
+      }
+      // 16-byte reads, the fill's own lane map
+      for (uint32_t v = threadIdx.x; v < n_vec; v += kSweepThreads) {
+        const uint4 got = lds_vec[v];
+        const uint4 want = lds_pattern_vec(seed, visit, v, inv);
+        st.see(got.x ^ want.x, 4 * v);
+        st.see(got.y ^ want.y, 4 * v + 1);
+        st.see(got.z ^ want.z, 4 * v + 2);
+        st.see(got.w ^ want.w, 4 * v + 3);
+      }
+      // dword reads, rotated lane map
+      for (uint32_t i = threadIdx.x; i < n_words; i += kSweepThreads) {
+        uint32_t w = i + rot;
+        if (w >= n_words) w -= n_words;
+        const uint32_t want =
+            gh::pattern_word(seed, gh::lds_pattern_index(visit, w)) ^ inv;
+        st.see(lds_words[w] ^ want, w);
+      }
+    }
+  }
+
+  // 3. exact MFMA on the SIMD this wave sits on
+  const uint32_t wg = visit * kSweepWaves + wave;
+  const bool inj_here = inj.mfma_on && visit == inj.mfma_visit && wave == inj.mfma_wave;
+  unsigned int mfma_bad[gh::kNumDtypes];
+  mfma_bad[gh::BF16] = sweep_mfma_bad<gh::BF16>(
+      seed, wg, lane, inj_here && inj.mfma_dtype == gh::BF16, inj.mfma_element, inj.mfma_mask);
+  mfma_bad[gh::F16] = sweep_mfma_bad<gh::F16>(
+      seed, wg, lane, inj_here && inj.mfma_dtype == gh::F16, inj.mfma_element, inj.mfma_mask);
+  mfma_bad[gh::FP8] = sweep_mfma_bad<gh::FP8>(
+      seed, wg, lane, inj_here && inj.mfma_dtype == gh::FP8, inj.mfma_element, inj.mfma_mask);
+  mfma_bad[gh::MXFP4] = sweep_mfma_bad<gh::MXFP4>(
+      seed, wg, lane, inj_here && inj.mfma_dtype == gh::MXFP4, inj.mfma_element, inj.mfma_mask);
+
+  // 4. publish: wave reductions, then lane 0 alone; fault fields only when set
+  const bool lds_faulty = __ballot(st.bad != 0) != 0;
+  LdsStats ws{0, 0, kNoBadWord, 0, 0};
+  if (lds_faulty) {
+    ws.bad_words = wave_sum_u64(st.bad);
+    ws.flipped_bits = wave_sum_u64(st.bits);
+    ws.first_bad_word = wave_min_u64(st.first);
+    ws.bad_bit_mask = wave_or_u32(st.mask);
+  }
+  for (int dt = 0; dt < gh::kNumDtypes; ++dt) {
+    if (__ballot(mfma_bad[dt] != 0) == 0) continue;
+    const unsigned int bad = (unsigned int)wave_sum_u64(mfma_bad[dt]);
+    if (lane == 0) atomicAdd(&slot->mfma_bad[loc.simd][dt], bad);
+  }
+  if (lane != 0) return;
+  atomicOr(&slot->simd_seen, 1u << loc.simd);
+  if (lds_faulty) {
+    atomicAdd(&slot->lds.bad_words, ws.bad_words);
+    atomicAdd(&slot->lds.flipped_bits, ws.flipped_bits);
+    atomicMin(&slot->lds.first_bad_word, ws.first_bad_word);
+    atomicOr(&slot->lds.bad_bit_mask, ws.bad_bit_mask);
+  }
+  rec->simd[wave] = loc.simd;
+  rec->lds[wave] = ws;
+  if (wave == 0) {
+    atomicAdd(&slot->visits, 1u);
+    rec->key = key;
+    rec->xcc_id_reg = xcc_reg;
+    rec->hw_id_reg = hw_reg;
+    rec->written = 1;
+  }
+}
+
+// test hook: the production fill, then the whole LDS copied out. The LDS is
+// preset first, so a word the fill skips reads back as 0x5A bytes.
+__global__ __launch_bounds__(kSweepThreads) void cu_lds_dump_kernel(
+    uint32_t* __restrict__ out, uint32_t lds_bytes, uint32_t seed, uint32_t visit,
+    uint32_t invert_mask) {
+  extern __shared__ uint4 lds_vec[];
+  uint32_t* lds_words = (uint32_t*)lds_vec;
+  const uint32_t n_words = lds_bytes / 4;
+  for (uint32_t i = threadIdx.x; i < n_words; i += kSweepThreads) lds_words[i] = 0x5A5A5A5Au;
+  __syncthreads();
+  lds_fill(lds_vec, lds_bytes / 16, seed, visit, invert_mask);
+  __syncthreads();
+  for (uint32_t i = threadIdx.x; i < n_words; i += kSweepThreads) out[i] = lds_words[i];
+}
+
+static int current_device_attribute(hipDeviceAttribute_t attr) {
+  int device = 0, value = 0;
+  HIP_CHECK(hipGetDevice(&device));
+  HIP_CHECK(hipDeviceGetAttribute(&value, attr, device));
+  return value;
+}
+
+// 0 stands for the device's maximum, at which one workgroup owns a CU
+static uint32_t checked_lds_bytes(uint64_t lds_bytes) {
+  const uint64_t max_bytes =
+      (uint64_t)current_device_attribute(hipDeviceAttributeMaxSharedMemoryPerBlock) & ~15ull;
+  if (lds_bytes == 0) lds_bytes = max_bytes;
+  if (lds_bytes < 16 || lds_bytes % 16 != 0 || lds_bytes > max_bytes)
+    throw py::value_error("lds_bytes must be a positive multiple of 16, at most " +
+                          std::to_string(max_bytes) + " on this device");
+  return (uint32_t)lds_bytes;
+}
+
+template <typename Kernel>
+static void allow_dynamic_lds(Kernel kernel, uint32_t lds_bytes) {
+  HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel),
+                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
+}
+
+constexpr int kSweepMaxPasses = 64;
+constexpr int kSweepMaxRounds = 64;
+constexpr int kSweepMaxBlocksPerRound = 1 << 14;
+constexpr uint64_t kSweepMaxVisits = 1ull << 18;
+
+struct CuSweepResult {
+  int cu_total = 0;
+  int rounds = 0;
+  uint32_t lds_bytes = 0;
+  int blocks_per_round = 0;
+  double elapsed_ms = 0.0;
+  std::vector<CuSlot> slots;
+  bool have_record = false;  // the injected visit was launched
+  CuRecord record{};
+};
+
+static int covered_slots(const std::vector<CuSlot>& slots) {
+  int n = 0;
+  for (const CuSlot& s : slots) n += s.visits != 0;
+  return n;
+}
+
+// Rounds of blocks_per_round workgroups (0: 4 x CUs) until as many slots have
+// been visited as the device has CUs, or max_rounds. inject names visits of
+// the whole run: visit = round * blocks_per_round + block.
+static CuSweepResult run_cu_sweep(uint32_t seed, int passes, uint64_t lds_bytes,
+                                  int blocks_per_round, int max_rounds,
+                                  const CuInject& inject) {
+  CuSweepResult res;
+  res.cu_total = current_device_attribute(hipDeviceAttributeMultiprocessorCount);
+  res.lds_bytes = checked_lds_bytes(lds_bytes);
+  if (passes < 1 || passes > kSweepMaxPasses)
+    throw py::value_error("passes must be in [1, " + std::to_string(kSweepMaxPasses) + "]");
+  if (max_rounds < 1 || max_rounds > kSweepMaxRounds)
+    throw py::value_error("max_rounds must be in [1, " + std::to_string(kSweepMaxRounds) + "]");
+  if (blocks_per_round == 0) blocks_per_round = 4 * res.cu_total;
+  if (blocks_per_round < 1 || blocks_per_round > kSweepMaxBlocksPerRound)
+    throw py::value_error("blocks_per_round must be 0 or in [1, " +
+                          std::to_string(kSweepMaxBlocksPerRound) + "]");
+  const uint64_t visits = (uint64_t)blocks_per_round * max_rounds;
+  if (visits > kSweepMaxVisits)
+    throw py::value_error("blocks_per_round x max_rounds must be at most " +
+                          std::to_string(kSweepMaxVisits));
+  if (inject.lds_on) {
+    if (inject.lds_visit >= visits)
+      throw py::value_error("injected visit is outside [0, blocks_per_round x max_rounds)");
+    if (inject.lds_word >= res.lds_bytes / 4)
+      throw py::value_error("injected LDS word is outside the checked range");
+  }
+  if (inject.mfma_on && inject.mfma_visit >= visits)
+    throw py::value_error("injected visit is outside [0, blocks_per_round x max_rounds)");
+  res.blocks_per_round = blocks_per_round;
+
+  DeviceScope scope;
+  CuSlot clean{};
+  clean.lds.first_bad_word = kNoBadWord;
+  res.slots.assign(gh::kCuSlots, clean);
+  const size_t slot_bytes = gh::kCuSlots * sizeof(CuSlot);
+  CuSlot* d_slots = (CuSlot*)scope.alloc(slot_bytes);
+  CuRecord* d_records = (CuRecord*)scope.alloc(visits * sizeof(CuRecord));
+  HIP_CHECK(hipMemcpy(d_slots, res.slots.data(), slot_bytes, hipMemcpyHostToDevice));
+  HIP_CHECK(hipMemset(d_records, 0, visits * sizeof(CuRecord)));
+  allow_dynamic_lds(cu_sweep_kernel, res.lds_bytes);
+
+  hipEvent_t t0 = scope.event(), t1 = scope.event();
+  HIP_CHECK(hipEventRecord(t0, 0));
+  while (res.rounds < max_rounds) {
+    hipLaunchKernelGGL(cu_sweep_kernel, dim3(blocks_per_round), dim3(kSweepThreads),
+                       res.lds_bytes, 0, d_slots, d_records,
+                       (uint32_t)(res.rounds * blocks_per_round), seed, passes,
+                       res.lds_bytes, inject);
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipMemcpy(res.slots.data(), d_slots, slot_bytes, hipMemcpyDeviceToHost));
+    ++res.rounds;
+    if (covered_slots(res.slots) >= res.cu_total) break;
+  }
+  HIP_CHECK(hipEventRecord(t1, 0));
+  HIP_CHECK(hipEventSynchronize(t1));
+  float ms = 0.f;
+  HIP_CHECK(hipEventElapsedTime(&ms, t0, t1));
+  res.elapsed_ms = ms;
+
+  if (inject.lds_on || inject.mfma_on) {
+    const uint32_t visit = inject.lds_on ? inject.lds_visit : inject.mfma_visit;
+    if (visit < (uint64_t)res.rounds * blocks_per_round) {
+      HIP_CHECK(hipMemcpy(&res.record, d_records + visit, sizeof(CuRecord),
+                          hipMemcpyDeviceToHost));
+      res.have_record = res.record.written != 0;
+    }
+  }
+  return res;
+}
+
+static std::string run_debug_cu_lds_dump(uint64_t lds_bytes, uint32_t seed, bool invert,
+                                         uint32_t visit) {
+  const uint32_t bytes = checked_lds_bytes(lds_bytes);
+  DeviceScope scope;
+  uint32_t* d_out = (uint32_t*)scope.alloc(bytes);
+  HIP_CHECK(hipMemset(d_out, 0xA5, bytes));
+  allow_dynamic_lds(cu_lds_dump_kernel, bytes);
+  hipLaunchKernelGGL(cu_lds_dump_kernel, dim3(1), dim3(kSweepThreads), bytes, 0, d_out,
+                     bytes, seed, visit, invert ? 0xFFFFFFFFu : 0u);
+  HIP_CHECK(hipGetLastError());
+  HIP_CHECK(hipDeviceSynchronize());
+  std::string host(bytes, '\0');
+  HIP_CHECK(hipMemcpy(&host[0], d_out, bytes, hipMemcpyDeviceToHost));
+  return host;
+}
+
+// ---------------------------------------------------------------------------
 // host API
 // ---------------------------------------------------------------------------
 static py::dict device_info(int device) {
@@ -897,7 +1270,163 @@ static matrix_t reference_tile_py(const std::string& dtype, uint32_t seed,
 
 static const char* const kDtypeNames[gh::kNumDtypes] = {"bf16", "f16", "fp8", "mxfp4"};
 
-static py::dict burn_in(int device, double hbm_fraction, double hbm_floor_gb_s) {
+// -- CU sweep bindings -------------------------------------------------------
+typedef std::optional<std::tuple<int64_t, int64_t, int64_t, int64_t>> inject_lds_t;
+typedef std::optional<std::tuple<int64_t, int64_t, std::string, int64_t, int64_t>> inject_mfma_t;
+
+static uint32_t checked_mask(int64_t mask) {
+  if (mask <= 0 || mask > 0xFFFFFFFFll)
+    throw py::value_error("xor mask must be a non-zero 32-bit value");
+  return (uint32_t)mask;
+}
+
+static uint32_t checked_index(int64_t v, uint64_t limit, const char* what) {
+  if (v < 0 || (uint64_t)v >= limit)
+    throw py::value_error(std::string(what) + " is outside the checked range");
+  return (uint32_t)v;
+}
+
+// everything that does not depend on the device; run_cu_sweep checks the rest
+static CuInject checked_inject(const inject_lds_t& lds, const inject_mfma_t& mfma) {
+  CuInject inj;
+  if (lds) {
+    const auto& [visit, word, mask, phase] = *lds;
+    inj.lds_on = 1;
+    inj.lds_visit = checked_index(visit, kSweepMaxVisits, "injected visit");
+    inj.lds_word = checked_index(word, 1ull << 30, "injected LDS word");
+    inj.lds_mask = checked_mask(mask);
+    inj.lds_phase = checked_index(phase, 2, "injected phase");
+  }
+  if (mfma) {
+    const auto& [visit, wave, dtype, element, mask] = *mfma;
+    inj.mfma_on = 1;
+    inj.mfma_visit = checked_index(visit, kSweepMaxVisits, "injected visit");
+    inj.mfma_wave = checked_index(wave, kSweepWaves, "injected wave");
+    inj.mfma_dtype = (uint32_t)parse_dtype(dtype);
+    inj.mfma_element = checked_index(element, 256, "injected D element");
+    inj.mfma_mask = checked_mask(mask);
+  }
+  if (lds && mfma && inj.lds_visit != inj.mfma_visit)
+    throw py::value_error("inject_lds and inject_mfma must name the same visit");
+  return inj;
+}
+
+static py::dict location_dict(uint32_t key) {
+  const gh::CuLocation loc = gh::location_of_key(key);
+  py::dict d;
+  d["xcc"] = loc.xcc;
+  d["se"] = loc.se;
+  d["sh"] = loc.sh;
+  d["cu"] = loc.cu;
+  return d;
+}
+
+static py::dict lds_stats_dict(const LdsStats& s) {
+  py::dict d;
+  d["bad_words"] = s.bad_words;
+  d["flipped_bits"] = s.flipped_bits;
+  d["bad_bit_mask"] = s.bad_bit_mask;
+  d["first_bad_word"] = s.first_bad_word == kNoBadWord ? (int64_t)-1
+                                                       : (int64_t)s.first_bad_word;
+  return d;
+}
+
+static bool slot_faulty(const CuSlot& s) {
+  if (s.lds.bad_words != 0) return true;
+  for (uint32_t simd = 0; simd < gh::kNumSimds; ++simd)
+    for (int dt = 0; dt < gh::kNumDtypes; ++dt)
+      if (s.mfma_bad[simd][dt] != 0) return true;
+  return false;
+}
+
+static py::dict cu_sweep_dict(const CuSweepResult& r, bool injected) {
+  constexpr unsigned int kAllSimds = (1u << gh::kNumSimds) - 1u;
+  py::dict d, xcc_covered;
+  py::list faulty, locations;
+  int covered = 0;
+  bool simd_complete = true;
+  for (uint32_t key = 0; key < gh::kCuSlots; ++key) {
+    const CuSlot& s = r.slots[key];
+    if (s.visits == 0) continue;
+    ++covered;
+    simd_complete = simd_complete && s.simd_seen == kAllSimds;
+    py::dict where = location_dict(key);
+    py::object xcc = where["xcc"];
+    xcc_covered[xcc] = (xcc_covered.contains(xcc) ? xcc_covered[xcc].cast<int>() : 0) + 1;
+    if (slot_faulty(s)) {
+      py::dict f = location_dict(key);
+      f["lds"] = lds_stats_dict(s.lds);
+      py::list mfma;
+      for (uint32_t simd = 0; simd < gh::kNumSimds; ++simd)
+        for (int dt = 0; dt < gh::kNumDtypes; ++dt)
+          if (s.mfma_bad[simd][dt] != 0) mfma.append(py::make_tuple(simd, kDtypeNames[dt]));
+      f["mfma"] = mfma;
+      faulty.append(f);
+    }
+    where["visits"] = s.visits;
+    where["simd_seen"] = s.simd_seen;
+    locations.append(where);
+  }
+  d["cu_total"] = r.cu_total;
+  d["cu_covered"] = covered;
+  d["rounds"] = r.rounds;
+  d["lds_bytes"] = r.lds_bytes;
+  d["blocks_per_round"] = r.blocks_per_round;
+  d["elapsed_ms"] = r.elapsed_ms;
+  d["xcc_covered"] = xcc_covered;
+  d["simd_complete"] = simd_complete;
+  d["faulty"] = faulty;
+  d["locations"] = locations;
+  if (injected) {
+    if (!r.have_record) {
+      d["record"] = py::none();
+    } else {
+      py::dict rec = location_dict(r.record.key);
+      LdsStats sum{0, 0, kNoBadWord, 0, 0};
+      py::list simd;
+      for (int w = 0; w < kSweepWaves; ++w) {
+        simd.append(r.record.simd[w]);
+        sum.bad_words += r.record.lds[w].bad_words;
+        sum.flipped_bits += r.record.lds[w].flipped_bits;
+        sum.first_bad_word = std::min(sum.first_bad_word, r.record.lds[w].first_bad_word);
+        sum.bad_bit_mask |= r.record.lds[w].bad_bit_mask;
+      }
+      rec["simd"] = simd;
+      rec["lds"] = lds_stats_dict(sum);
+      rec["xcc_id_reg"] = r.record.xcc_id_reg;
+      rec["hw_id_reg"] = r.record.hw_id_reg;
+      d["record"] = rec;
+    }
+  }
+  return d;
+}
+
+static py::dict cu_sweep(int device, uint32_t seed, int passes, uint64_t lds_bytes,
+                         int blocks_per_round, int max_rounds, inject_lds_t inject_lds,
+                         inject_mfma_t inject_mfma) {
+  const CuInject inj = checked_inject(inject_lds, inject_mfma);
+  use_device(device);
+  return cu_sweep_dict(run_cu_sweep(seed, passes, lds_bytes, blocks_per_round, max_rounds, inj),
+                       inj.lds_on || inj.mfma_on);
+}
+
+static py::dict decode_location_py(uint32_t xcc_id_reg, uint32_t hw_id_reg) {
+  const gh::CuLocation loc = gh::decode_location(xcc_id_reg, hw_id_reg);
+  py::dict d = location_dict(gh::location_key(loc));
+  d["simd"] = loc.simd;
+  d["key"] = gh::location_key(loc);
+  return d;
+}
+
+static py::bytes debug_cu_lds_dump(int device, uint64_t lds_bytes, uint32_t seed, bool invert,
+                                   int64_t visit) {
+  const uint32_t v = checked_index(visit, 1ull << 32, "visit");
+  use_device(device);
+  return py::bytes(run_debug_cu_lds_dump(lds_bytes, seed, invert, v));
+}
+
+static py::dict burn_in(int device, double hbm_fraction, double hbm_floor_gb_s,
+                        bool require_cu_coverage) {
   py::dict result = health_check(device, hbm_floor_gb_s, false);
   bool healthy = result["healthy"].cast<bool>();
   py::dict exact, first_bad;
@@ -914,7 +1443,16 @@ static py::dict burn_in(int device, double hbm_fraction, double hbm_floor_gb_s) 
   result["mfma_first_bad"] = first_bad;
   result["hbm_pattern_ok"] = pattern_ok;
   result["hbm_pattern"] = pattern_dict(p);
-  result["healthy"] = healthy && pattern_ok;
+  // every CU's LDS and every SIMD's matrix pipe, with the place of a fault.
+  // Incomplete coverage is reported and fatal only on request: a CU mask or a
+  // co-tenant can legitimately keep CUs away from this process.
+  const py::dict sweep = cu_sweep_dict(run_cu_sweep(gh::kDefaultSeed, 1, 0, 0, 8, CuInject{}), false);
+  const bool cu_ok = py::len(sweep["faulty"]) == 0;
+  const bool cu_complete = sweep["cu_covered"].cast<int>() >= sweep["cu_total"].cast<int>();
+  result["cu_sweep"] = sweep;
+  result["cu_ok"] = cu_ok;
+  result["cu_coverage_complete"] = cu_complete;
+  result["healthy"] = healthy && pattern_ok && cu_ok && (cu_complete || !require_cu_coverage);
   return result;
 }
 
@@ -949,7 +1487,15 @@ PYBIND11_MODULE(gpuhealth, m) {
         py::arg("dtype") = "bf16", py::arg("seed") = gh::kDefaultSeed,
         py::arg("workgroup") = 0);
   m.def("burn_in", &burn_in, py::arg("device") = 0, py::arg("hbm_fraction") = 0.9,
-        py::arg("hbm_floor_gb_s") = 1000.0);
+        py::arg("hbm_floor_gb_s") = 1000.0, py::arg("require_cu_coverage") = false);
+  m.def("cu_sweep", &cu_sweep, py::arg("device") = 0, py::arg("seed") = gh::kDefaultSeed,
+        py::arg("passes") = 1, py::arg("lds_bytes") = 0, py::arg("blocks_per_round") = 0,
+        py::arg("max_rounds") = 8, py::arg("inject_lds") = py::none(),
+        py::arg("inject_mfma") = py::none());
+  m.def("decode_location", &decode_location_py, py::arg("xcc_id_reg"), py::arg("hw_id_reg"));
+  m.def("debug_cu_lds_dump", &debug_cu_lds_dump, py::arg("device") = 0,
+        py::arg("lds_bytes") = 0, py::arg("seed") = gh::kDefaultSeed,
+        py::arg("invert") = false, py::arg("visit") = 0);
   m.def("device_count", &device_count);
   m.def("device_info", &device_info, py::arg("device") = 0);
   m.def("mfma_smoke", &mfma_smoke, py::arg("device") = 0,

@@ -63,6 +63,74 @@ GH_HD inline uint32_t pattern_word(uint32_t seed, uint64_t word_index) {
 }
 
 // ---------------------------------------------------------------------------
+// CU sweep: where a wave runs, and the LDS march pattern
+//
+// decode_location takes the raw values of the XCC_ID and HW_ID hardware
+// registers. The masks below are the only place the register layout is written
+// down. They follow the GCN/CDNA HW_ID layout as the HIP headers document it
+// for the gfx942 family (SIMD_ID 5:4, CU_ID 11:8, SH_ID 12, SE_ID 14:13: four
+// shader engines per XCC; bit 15 belongs to SE_ID only on the single-die
+// gfx908/gfx90a) and XCC_ID 3:0 of its own register. The layout is right
+// exactly when a saturating sweep observes as many distinct location keys as
+// the device has CUs (tests/test_gpu_cu_sweep.py): a field that is too narrow
+// merges CUs and gives too few, a mask that takes in bits of a neighbouring
+// field (wave slot, pipe, thread-group id) splits CUs and gives too many.
+// ---------------------------------------------------------------------------
+struct CuLocation {
+  uint32_t xcc, se, sh, cu, simd;
+};
+
+constexpr uint32_t kXccShift = 0, kXccBits = 4;    // XCC_ID register
+constexpr uint32_t kSimdShift = 4, kSimdBits = 2;  // HW_ID register from here on
+constexpr uint32_t kCuShift = 8, kCuBits = 4;
+constexpr uint32_t kShShift = 12, kShBits = 1;
+constexpr uint32_t kSeShift = 13, kSeBits = 2;
+constexpr uint32_t kNumSimds = 1u << kSimdBits;
+// one slot per (xcc, se, sh, cu) the fields can name
+constexpr uint32_t kCuSlots = 1u << (kXccBits + kSeBits + kShBits + kCuBits);
+
+GH_HD inline uint32_t reg_field(uint32_t reg, uint32_t shift, uint32_t bits) {
+  return (reg >> shift) & ((1u << bits) - 1u);
+}
+
+GH_HD inline CuLocation decode_location(uint32_t xcc_id_reg, uint32_t hw_id_reg) {
+  CuLocation loc;
+  loc.xcc = reg_field(xcc_id_reg, kXccShift, kXccBits);
+  loc.se = reg_field(hw_id_reg, kSeShift, kSeBits);
+  loc.sh = reg_field(hw_id_reg, kShShift, kShBits);
+  loc.cu = reg_field(hw_id_reg, kCuShift, kCuBits);
+  loc.simd = reg_field(hw_id_reg, kSimdShift, kSimdBits);
+  return loc;
+}
+
+// dense index over (xcc, se, sh, cu), below kCuSlots; the SIMD is not part of it
+GH_HD inline uint32_t location_key(const CuLocation& loc) {
+  return (((loc.xcc << kSeBits | loc.se) << kShBits | loc.sh) << kCuBits) | loc.cu;
+}
+
+// inverse of location_key (simd = 0)
+GH_HD inline CuLocation location_of_key(uint32_t key) {
+  CuLocation loc;
+  loc.cu = key & ((1u << kCuBits) - 1u);
+  key >>= kCuBits;
+  loc.sh = key & ((1u << kShBits) - 1u);
+  key >>= kShBits;
+  loc.se = key & ((1u << kSeBits) - 1u);
+  key >>= kSeBits;
+  loc.xcc = key & ((1u << kXccBits) - 1u);
+  loc.simd = 0;
+  return loc;
+}
+
+// LDS word `word` of workgroup visit `visit` holds
+// pattern_word(seed, lds_pattern_index(visit, word)) ^ invert: the visit is the
+// high half of the index and so selects the bijection, every visit of a CU
+// sees different data.
+GH_HD inline uint64_t lds_pattern_index(uint32_t visit, uint32_t word) {
+  return (uint64_t)visit << 32 | word;
+}
+
+// ---------------------------------------------------------------------------
 // operand generators
 // ---------------------------------------------------------------------------
 enum Which : uint32_t { GEN_A = 0, GEN_B = 1, GEN_C = 2, GEN_SA = 3, GEN_SB = 4 };

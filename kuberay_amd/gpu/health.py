@@ -10,7 +10,7 @@ from __future__ import annotations
 
 import os
 from dataclasses import dataclass
-from typing import Dict, Optional
+from typing import Dict, List, Optional
 
 from . import rocm_smi
 
@@ -53,6 +53,10 @@ class HealthReport:
     hbm_pattern_ok: Optional[bool] = None
     hbm_bytes_checked: Optional[int] = None
     hbm_flipped_bits: Optional[int] = None
+    # CU sweep of the burn-in level; None when the native module has none
+    cu_total: Optional[int] = None
+    cu_covered: Optional[int] = None
+    cu_faulty: Optional[List[str]] = None
 
 
 def _rocm_smi_ok() -> bool:
@@ -111,12 +115,35 @@ def check_gpu_health(device: int = 0, quick: bool = False,
 DEFAULT_BURN_IN_HBM_FRACTION = 0.9
 
 
+def _cu_name(where, short: bool = False) -> str:
+    if short:
+        return f"xcc{where['xcc']}/se{where['se']}/cu{where['cu']}"
+    return f"xcc{where['xcc']}/se{where['se']}/sh{where['sh']}/cu{where['cu']}"
+
+
+def _cu_problem(where) -> str:
+    """One faulty CU of the sweep: where, and what its LDS and SIMDs showed."""
+    parts = []
+    lds = where.get("lds") or {}
+    if lds.get("bad_words"):
+        parts.append(f"lds {lds['bad_words']} bad words mask "
+                     f"0x{lds['bad_bit_mask']:08x} first word "
+                     f"{lds['first_bad_word']}")
+    for simd, dtype in where.get("mfma") or ():
+        parts.append(f"mfma {dtype} on simd {simd}")
+    return f"cu {_cu_name(where)}: " + "; ".join(parts)
+
+
 def check_gpu_burn_in(device: int = 0,
                       hbm_fraction: float = DEFAULT_BURN_IN_HBM_FRACTION,
-                      hbm_floor_gb_s: float = DEFAULT_HBM_FLOOR_GB_S) -> HealthReport:
+                      hbm_floor_gb_s: float = DEFAULT_HBM_FLOOR_GB_S,
+                      require_cu_coverage: bool = False) -> HealthReport:
     """Burn-in level: the full gate of ``check_gpu_health``, then the exact
     MFMA verification on the bf16, f16, fp8 and MXFP4 data paths, then a
-    data-verifying pattern sweep over ``hbm_fraction`` of the free HBM.
+    data-verifying pattern sweep over ``hbm_fraction`` of the free HBM, then
+    the CU sweep (LDS march on every CU, the exact MFMA tiles on every SIMD).
+    A faulty CU is unhealthy and named in ``detail``; CUs the sweep did not
+    reach are reported, and unhealthy only with ``require_cu_coverage``.
     Raises GpuHealthError on non-GPU hosts; ``detail`` names what failed."""
     if not gpu_node():
         raise GpuHealthError("not a GPU node (/dev/kfd missing)")
@@ -147,14 +174,28 @@ def check_gpu_burn_in(device: int = 0,
             f"{pattern['flipped_bits']} flipped bits, mask "
             f"0x{pattern['bad_bit_mask']:08x}, first bad offset "
             f"{pattern['first_bad_offset']}")
+    # a native module without the CU sweep gives the report it always gave
+    sweep = result.get("cu_sweep")
+    healthy = bool(result["healthy"])
+    cu_total = cu_covered = cu_faulty = None
+    if sweep is not None:
+        cu_total, cu_covered = int(sweep["cu_total"]), int(sweep["cu_covered"])
+        cu_faulty = [_cu_name(f, short=True) for f in sweep["faulty"]]
+        problems.extend(_cu_problem(f) for f in sweep["faulty"])
+        healthy = healthy and bool(result.get("cu_ok", not cu_faulty))
+        if not result.get("cu_coverage_complete", cu_covered >= cu_total):
+            problems.append(f"cu coverage {cu_covered}/{cu_total} after "
+                            f"{sweep['rounds']} rounds")
+            healthy = healthy and not require_cu_coverage
     if not rocm_ok:
         problems.append("rocm-smi did not respond")
     return HealthReport(
-        healthy=bool(result["healthy"]) and rocm_ok,
+        healthy=healthy and rocm_ok,
         mfma_ok=bool(result["mfma_ok"]),
         hbm_gb_s=float(result["hbm_gb_s"]),
         rocm_smi_ok=rocm_ok,
         detail="; ".join(problems),
+        cu_total=cu_total, cu_covered=cu_covered, cu_faulty=cu_faulty,
         mfma_exact=exact,
         hbm_pattern_ok=bool(result["hbm_pattern_ok"]),
         hbm_bytes_checked=int(pattern["bytes_checked"]),

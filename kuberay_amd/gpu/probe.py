@@ -3,9 +3,11 @@
 Injected into GPU worker readiness probes by the pod builder
 (common/pod.py init_liveness_and_readiness_probe). Exit 0 = healthy.
 
-``--deep [--hbm-fraction F]`` runs the burn-in level instead (HBM pattern
-sweep + exact MFMA checks); the pod builder injects it as a startupProbe on
-GPU workers whose template carries ``amd.com/gpu-burn-in: "true"``.
+``--deep [--hbm-fraction F] [--require-cu-coverage]`` runs the burn-in level
+instead (HBM pattern sweep + exact MFMA checks + the per-CU sweep of LDS and
+SIMDs; with the flag, a CU the sweep could not reach fails it); the pod
+builder injects it as a startupProbe on GPU workers whose template carries
+``amd.com/gpu-burn-in: "true"``.
 """
 from __future__ import annotations
 
@@ -30,13 +32,17 @@ def main(argv=None) -> int:
     parser.add_argument("--hbm-fraction", type=float,
                         default=DEFAULT_BURN_IN_HBM_FRACTION,
                         help="with --deep: fraction of the free HBM to sweep")
+    parser.add_argument("--require-cu-coverage", action="store_true",
+                        help="with --deep: unhealthy unless the CU sweep "
+                             "reached every CU of the device")
     args = parser.parse_args(argv)
 
     try:
         if args.deep:
             report = check_gpu_burn_in(device=args.device,
                                        hbm_fraction=args.hbm_fraction,
-                                       hbm_floor_gb_s=args.hbm_floor_gb_s)
+                                       hbm_floor_gb_s=args.hbm_floor_gb_s,
+                                       require_cu_coverage=args.require_cu_coverage)
         else:
             report = check_gpu_health(device=args.device, quick=args.quick,
                                       hbm_floor_gb_s=args.hbm_floor_gb_s)
@@ -44,21 +50,29 @@ def main(argv=None) -> int:
         print(f"gpu probe error: {e}", file=sys.stderr)
         return 2
     if args.deep:
+        # the CU sweep's fields appear when the native module ran one
+        swept = report.cu_total is not None
         if args.json_out:
-            print(json.dumps({
+            out = {
                 "healthy": report.healthy, "mfma_ok": report.mfma_ok,
                 "hbm_gb_s": report.hbm_gb_s, "rocm_smi_ok": report.rocm_smi_ok,
                 "detail": report.detail, "mfma_exact": report.mfma_exact,
                 "hbm_pattern_ok": report.hbm_pattern_ok,
                 "hbm_bytes_checked": report.hbm_bytes_checked,
-                "hbm_flipped_bits": report.hbm_flipped_bits}))
+                "hbm_flipped_bits": report.hbm_flipped_bits}
+            if swept:
+                out.update(cu_total=report.cu_total, cu_covered=report.cu_covered,
+                           cu_faulty=report.cu_faulty)
+            print(json.dumps(out))
         else:
+            cu = (f" cu_total={report.cu_total} cu_covered={report.cu_covered} "
+                  f"cu_faulty={report.cu_faulty}") if swept else ""
             print(f"healthy={report.healthy} mfma_ok={report.mfma_ok} "
                   f"hbm_gb_s={report.hbm_gb_s} rocm_smi_ok={report.rocm_smi_ok} "
                   f"mfma_exact={report.mfma_exact} "
                   f"hbm_pattern_ok={report.hbm_pattern_ok} "
                   f"hbm_bytes_checked={report.hbm_bytes_checked} "
-                  f"hbm_flipped_bits={report.hbm_flipped_bits}")
+                  f"hbm_flipped_bits={report.hbm_flipped_bits}{cu}")
             if report.detail:
                 print(report.detail, file=sys.stderr)
         return 0 if report.healthy else 1
