@@ -33,7 +33,12 @@
 //                    compares it, then repeats with the pattern inverted.
 //                    Reports mismatching words, flipped bits, the OR of the
 //                    differences (a stuck line is one bit) and the first bad
-//                    offset.
+//                    offset. Moving inversion is what catches a stuck-at bit
+//                    whichever value the pattern wanted there: shown with
+//                    hbm_pattern_check(stuck=), which forces bits of a word
+//                    after every fill; a single stuck bit is reported in
+//                    exactly one phase of every pass
+//                    (tests/test_gpu_input_faults.py).
 //   * mfma_exact   — asymmetric hashed operands whose products are exact in
 //                    fp32, through bf16, f16, OCP fp8 and block-scaled MXFP4
 //                    MFMA, with a C input; D is checked element by element
@@ -46,6 +51,19 @@
 //                    in [-8, 8], so the low mantissa bits of bf16 (4..0), f16
 //                    (7..0) and fp8 (0) are 0 in every operand: a stuck-at-0
 //                    fault there is outside what this data can show.
+//                    Shown on the device with operand-side seeded faults
+//                    (debug_mfma_dump / mfma_verify(inject_operand=), an xor
+//                    into one operand register of one lane before the MFMA;
+//                    tests/test_gpu_input_faults.py): which element of A, B,
+//                    C and of the scales each register of each lane is, that
+//                    the check flags a fault that came in through an operand
+//                    (the low mantissa bits and an infinity or NaN included),
+//                    and that the MX instruction takes the scale from byte 0
+//                    of its register alone and FP4 data from VGPRs 0..3 of
+//                    the eight-VGPR operand alone. Not shown: subnormal
+//                    operands; and the test flips the low mantissa bits, but
+//                    the production data still never sets them, so a
+//                    stuck-at-0 there stays invisible to the probe.
 //   * cu_sweep     — workgroups of four waves that each take the whole LDS of
 //                    a CU (the device's maximum per block, so one workgroup
 //                    owns its CU), read where they run (XCC_ID and HW_ID
@@ -65,8 +83,12 @@
 //                    another access pattern (ds_read_b64, transposed reads,
 //                    neighbouring-cell coupling), and which CU is missing —
 //                    only covered places are known. No workgroup waits on
-//                    another. Test hooks: cu_sweep(inject_lds=, inject_mfma=)
-//                    and debug_cu_lds_dump (the fill's LDS, copied out).
+//                    another. Test hooks: cu_sweep(inject_lds=, inject_mfma=,
+//                    inject_lds_stuck=) and debug_cu_lds_dump (the fill's LDS,
+//                    copied out). inject_lds_stuck forces bits of one LDS word
+//                    after every fill of one visit: a stuck bit is reported by
+//                    both verifies in exactly one phase of every pass, which
+//                    shows the march's own inversion and that every pass runs.
 //
 // What must agree between host and device (pattern, generators, encoders,
 // reference) is in gpuhealth_ref.hpp.
@@ -165,11 +187,61 @@ static corruptions_t checked_corruptions(corruptions_t c, uint64_t limit,
   return c;
 }
 
+static uint32_t checked_mask(int64_t mask) {
+  if (mask <= 0 || mask > 0xFFFFFFFFll)
+    throw py::value_error("xor mask must be a non-zero 32-bit value");
+  return (uint32_t)mask;
+}
+
+static uint32_t checked_index(int64_t v, uint64_t limit, const char* what) {
+  if (v < 0 || (uint64_t)v >= limit)
+    throw py::value_error(std::string(what) + " is outside the checked range");
+  return (uint32_t)v;
+}
+
 // host read-xor-write of one 32-bit word of device memory
 static void xor_device_word(void* addr, uint32_t mask) {
   uint32_t word = 0;
   HIP_CHECK(hipMemcpy(&word, addr, 4, hipMemcpyDeviceToHost));
   word ^= mask;
+  HIP_CHECK(hipMemcpy(addr, &word, 4, hipMemcpyHostToDevice));
+}
+
+// (index, mask, value) triples a test hands in: a stuck-at fault. After every
+// fill the masked bits of that 32-bit word are forced to value (0 or 1),
+// whatever the fill wrote there.
+struct StuckWord {
+  uint64_t word;
+  uint32_t mask, value;
+};
+typedef std::vector<std::tuple<int64_t, int64_t, int64_t>> stuck_t;
+
+// Sorted by index; the same rules as checked_corruptions, and value is 0 or 1.
+static std::vector<StuckWord> checked_stuck(stuck_t s, uint64_t limit, const char* what) {
+  std::sort(s.begin(), s.end());
+  std::vector<StuckWord> out;
+  for (size_t n = 0; n < s.size(); ++n) {
+    const auto& [word, mask, value] = s[n];
+    if (word < 0 || (uint64_t)word >= limit)
+      throw py::value_error(std::string(what) + " is outside the checked range");
+    if (value != 0 && value != 1) throw py::value_error("stuck value must be 0 or 1");
+    if (n > 0 && word == std::get<0>(s[n - 1]))
+      throw py::value_error(std::string(what) + " is named twice");
+    out.push_back({(uint64_t)word, checked_mask(mask), (uint32_t)value});
+  }
+  return out;
+}
+
+GH_HD inline uint32_t forced_word(uint32_t word, uint32_t mask, uint32_t value) {
+  return value ? (word | mask) : (word & ~mask);
+}
+
+// host read-force-write of one 32-bit word of device memory, the path of
+// xor_device_word
+static void force_device_word(void* addr, uint32_t mask, uint32_t value) {
+  uint32_t word = 0;
+  HIP_CHECK(hipMemcpy(&word, addr, 4, hipMemcpyDeviceToHost));
+  word = forced_word(word, mask, value);
   HIP_CHECK(hipMemcpy(addr, &word, 4, hipMemcpyHostToDevice));
 }
 
@@ -395,12 +467,16 @@ struct PatternResult {
 // and in the verify; everything reported stays relative to the sweep.
 // corruptions: (word, mask) relative to the sweep, applied between the fill and
 // the verify of pass corrupt_pass, phase corrupt_phase.
+// stuck: (word, mask, value) relative to the sweep, forced after every fill of
+// every pass and both phases, after the corruptions where both name a word (a
+// stuck bit stays stuck).
 static PatternResult run_hbm_pattern(uint64_t target_bytes, double fraction,
                                      uint32_t seed, int passes,
                                      uint64_t max_chunk_bytes,
                                      uint64_t pattern_base = 0,
                                      corruptions_t corruptions = {},
-                                     int corrupt_pass = 0, int corrupt_phase = 0) {
+                                     int corrupt_pass = 0, int corrupt_phase = 0,
+                                     stuck_t stuck_in = {}) {
   if (target_bytes == 0) {
     if (!(fraction > 0.0) || fraction > 1.0)
       throw py::value_error("fraction must be in (0, 1] when no size is given");
@@ -419,6 +495,8 @@ static PatternResult run_hbm_pattern(uint64_t target_bytes, double fraction,
   corruptions = checked_corruptions(std::move(corruptions), target_bytes / 4, "corrupted word");
   if (corrupt_pass < 0 || corrupt_pass >= passes || corrupt_phase < 0 || corrupt_phase > 1)
     throw py::value_error("corrupt_at must name a pass in [0, passes) and phase 0 or 1");
+  const std::vector<StuckWord> stuck =
+      checked_stuck(std::move(stuck_in), target_bytes / 4, "stuck word");
 
   struct Chunk { uint4* ptr; uint64_t bytes; uint64_t base_word; };
   DeviceScope scope;
@@ -440,6 +518,13 @@ static PatternResult run_hbm_pattern(uint64_t target_bytes, double fraction,
   if (chunks.empty()) throw std::runtime_error("could not allocate any device memory to sweep");
   if (!corruptions.empty() && (uint64_t)corruptions.back().first >= covered / 4)
     throw py::value_error("corrupted word is outside the memory that could be allocated");
+  if (!stuck.empty() && stuck.back().word >= covered / 4)
+    throw py::value_error("stuck word is outside the memory that could be allocated");
+  // the address of sweep word w; callers walk sorted lists, so ci only grows
+  auto word_addr = [&chunks](uint64_t w, size_t& ci) {
+    while (w >= chunks[ci].base_word + chunks[ci].bytes / 4) ++ci;
+    return (uint32_t*)chunks[ci].ptr + (w - chunks[ci].base_word);
+  };
 
   PatternStats* d_stats = (PatternStats*)scope.alloc(sizeof(PatternStats));
   PatternResult res;
@@ -457,13 +542,11 @@ static PatternResult run_hbm_pattern(uint64_t target_bytes, double fraction,
       if (pass == corrupt_pass && phase == corrupt_phase) {
         // both lists are sorted, so one walk finds every word's chunk
         size_t ci = 0;
-        for (const auto& [word, mask] : corruptions) {
-          const uint64_t w = (uint64_t)word;
-          while (w >= chunks[ci].base_word + chunks[ci].bytes / 4) ++ci;
-          xor_device_word((uint32_t*)chunks[ci].ptr + (w - chunks[ci].base_word),
-                          (uint32_t)mask);
-        }
+        for (const auto& [word, mask] : corruptions)
+          xor_device_word(word_addr((uint64_t)word, ci), (uint32_t)mask);
       }
+      size_t ci = 0;
+      for (const StuckWord& s : stuck) force_device_word(word_addr(s.word, ci), s.mask, s.value);
       for (const Chunk& c : chunks)
         launch_pattern_verify(c.ptr, c.bytes / 16, pattern_base + c.base_word, seed, inv,
                               d_stats);
@@ -557,15 +640,46 @@ static StreamCopyResult run_debug_stream_copy(uint64_t bytes, uint32_t seed) {
 //   C/D (all paths)     : register r = D[4g + r][i]
 // The maps are proven on the device by tests/test_gpu_burn_in.py and
 // tests/test_gpu_probe_kernels.py: with asymmetric hashed data D equals
-// A·B + C exactly only if all are right.
+// A·B + C exactly only if all are right, up to a mistake that A and B share
+// (j reversed in both, two k-groups swapped in both). Those are excluded by
+// tests/test_gpu_input_faults.py: a fault seeded into one register of one lane
+// changes D as this map says and not otherwise.
 // ---------------------------------------------------------------------------
 typedef __attribute__((ext_vector_type(8))) _Float16 frag_f16_t;
 typedef __attribute__((ext_vector_type(8))) int frag_i32x8_t;
+typedef __attribute__((ext_vector_type(4))) uint32_t frag_u32x4_t;
 
-template <int DT>
+// Test hook: an xor into one 32-bit register of one operand of one lane of one
+// workgroup, applied after the operands are packed and before the MFMA reads
+// them. reg counts the operand's dwords in that lane: 0..3 for bf16 / f16 A
+// and B (elements 2 reg and 2 reg + 1, the even one in the low half), 0..1 for
+// fp8 (bytes 4 reg .. 4 reg + 3), 0..7 for the eight-VGPR FP4 operand, 0..3
+// for C, 0 for a scale. Only the INJECT instantiations read it; the kernels of
+// burn_in() and of the CU sweep are the plain ones.
+enum Operand : uint32_t { OP_A = 0, OP_B = 1, OP_C = 2, OP_SA = 3, OP_SB = 4 };
+struct OperandInject {
+  uint32_t wg = 0, lane = 0, operand = 0, reg = 0, mask = 0;
+};
+
+// dwords of the A or B operand one lane holds
+static int operand_dwords(int dtype) {
+  return dtype == gh::MXFP4 ? 8 : (dtype == gh::FP8 ? 2 : 4);
+}
+
+// a ^= mask on dword reg of an N-dword operand register; no dynamic indexing
+template <int N, typename V>
+__device__ inline void xor_dword(V& v, uint32_t reg, uint32_t mask) {
+  for (uint32_t r = 0; r < (uint32_t)N; ++r) v[r] ^= (r == reg ? mask : 0u);
+}
+
+// inj_mask is zero in every lane but the injected one
+template <int DT, bool INJECT = false>
 __device__ inline frag_cd_t mfma_exact_tile(uint32_t seed, uint32_t wg, int lane,
-                                            frag_cd_t acc) {
+                                            frag_cd_t acc, uint32_t inj_operand = 0,
+                                            uint32_t inj_reg = 0, uint32_t inj_mask = 0) {
   const uint32_t i = lane & 15, g = lane >> 4;
+  const uint32_t mask_a = inj_operand == OP_A ? inj_mask : 0u;
+  const uint32_t mask_b = inj_operand == OP_B ? inj_mask : 0u;
   if constexpr (DT == gh::BF16) {
     frag_ab_t a, b;
     for (uint32_t j = 0; j < 8; ++j) {
@@ -573,6 +687,14 @@ __device__ inline frag_cd_t mfma_exact_tile(uint32_t seed, uint32_t wg, int lane
           (float)gh::gen_int(seed, wg, DT, gh::GEN_A, i, 8 * g + j)));
       b[j] = __builtin_bit_cast(__bf16, gh::f32_to_bf16(
           (float)gh::gen_int(seed, wg, DT, gh::GEN_B, i, 8 * g + j)));
+    }
+    if constexpr (INJECT) {
+      frag_u32x4_t ua = __builtin_bit_cast(frag_u32x4_t, a);
+      frag_u32x4_t ub = __builtin_bit_cast(frag_u32x4_t, b);
+      xor_dword<4>(ua, inj_reg, mask_a);
+      xor_dword<4>(ub, inj_reg, mask_b);
+      a = __builtin_bit_cast(frag_ab_t, ua);
+      b = __builtin_bit_cast(frag_ab_t, ub);
     }
     return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, acc, 0, 0, 0);
   } else if constexpr (DT == gh::F16) {
@@ -583,6 +705,14 @@ __device__ inline frag_cd_t mfma_exact_tile(uint32_t seed, uint32_t wg, int lane
       b[j] = __builtin_bit_cast(_Float16, gh::f32_to_f16(
           (float)gh::gen_int(seed, wg, DT, gh::GEN_B, i, 8 * g + j)));
     }
+    if constexpr (INJECT) {
+      frag_u32x4_t ua = __builtin_bit_cast(frag_u32x4_t, a);
+      frag_u32x4_t ub = __builtin_bit_cast(frag_u32x4_t, b);
+      xor_dword<4>(ua, inj_reg, mask_a);
+      xor_dword<4>(ub, inj_reg, mask_b);
+      a = __builtin_bit_cast(frag_f16_t, ua);
+      b = __builtin_bit_cast(frag_f16_t, ub);
+    }
     return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, acc, 0, 0, 0);
   } else if constexpr (DT == gh::FP8) {
     uint64_t a = 0, b = 0;
@@ -591,6 +721,10 @@ __device__ inline frag_cd_t mfma_exact_tile(uint32_t seed, uint32_t wg, int lane
                (float)gh::gen_int(seed, wg, DT, gh::GEN_A, i, 8 * g + j)) << (8 * j);
       b |= (uint64_t)gh::f32_to_e4m3(
                (float)gh::gen_int(seed, wg, DT, gh::GEN_B, i, 8 * g + j)) << (8 * j);
+    }
+    if constexpr (INJECT) {
+      a ^= (uint64_t)mask_a << (32 * (inj_reg & 1u));
+      b ^= (uint64_t)mask_b << (32 * (inj_reg & 1u));
     }
     return __builtin_amdgcn_mfma_f32_16x16x32_fp8_fp8((long)a, (long)b, acc, 0, 0, 0);
   } else {
@@ -605,25 +739,53 @@ __device__ inline frag_cd_t mfma_exact_tile(uint32_t seed, uint32_t wg, int lane
       a[v] = (int)wa;
       b[v] = (int)wb;
     }
-    const int sa = (int)gh::gen_scale(seed, wg, gh::GEN_SA, i, g);
-    const int sb = (int)gh::gen_scale(seed, wg, gh::GEN_SB, i, g);
-    // cbsz=4 / blgp=4: FP4 A and B; opsel 0: scale is byte 0 of the operand
+    int sa = (int)gh::gen_scale(seed, wg, gh::GEN_SA, i, g);
+    int sb = (int)gh::gen_scale(seed, wg, gh::GEN_SB, i, g);
+    if constexpr (INJECT) {
+      xor_dword<8>(a, inj_reg, mask_a);
+      xor_dword<8>(b, inj_reg, mask_b);
+      sa ^= (int)(inj_operand == OP_SA ? inj_mask : 0u);
+      sb ^= (int)(inj_operand == OP_SB ? inj_mask : 0u);
+    }
+    // cbsz=4 / blgp=4: FP4 A and B, which the instruction takes from VGPRs 0..3
+    // of each eight-VGPR operand; opsel 0: the scale is byte 0 of its register
     return __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(a, b, acc, 4, 4, 0, sa, 0, sb);
   }
 }
 
 // one wave per workgroup; D tiles are row-major, tile wg at out + 256 * wg
-template <int DT>
-__global__ void mfma_exact_kernel(float* __restrict__ out, uint32_t seed,
-                                  uint32_t wg_base) {
+template <int DT, bool INJECT>
+__device__ inline void mfma_exact_body(float* __restrict__ out, uint32_t seed,
+                                       uint32_t wg_base, const OperandInject& inj) {
   const int lane = threadIdx.x & 63;
   const uint32_t wg = wg_base + blockIdx.x;
   const uint32_t col = lane & 15, row0 = 4 * (lane >> 4);
   frag_cd_t acc;
   for (uint32_t r = 0; r < 4; ++r) acc[r] = (float)gh::gen_c(seed, wg, DT, row0 + r, col);
-  acc = mfma_exact_tile<DT>(seed, wg, lane, acc);
+  if constexpr (INJECT) {
+    const uint32_t mask = (wg == inj.wg && (uint32_t)lane == inj.lane) ? inj.mask : 0u;
+    for (uint32_t r = 0; r < 4; ++r)
+      if (inj.operand == OP_C && r == inj.reg)
+        acc[r] = gh::bits_f32(gh::f32_bits(acc[r]) ^ mask);
+    acc = mfma_exact_tile<DT, true>(seed, wg, lane, acc, inj.operand, inj.reg, mask);
+  } else {
+    acc = mfma_exact_tile<DT>(seed, wg, lane, acc);
+  }
   float* tile = out + (size_t)blockIdx.x * 256;
   for (uint32_t r = 0; r < 4; ++r) tile[(row0 + r) * 16 + col] = acc[r];
+}
+
+template <int DT>
+__global__ void mfma_exact_kernel(float* __restrict__ out, uint32_t seed,
+                                  uint32_t wg_base) {
+  mfma_exact_body<DT, false>(out, seed, wg_base, OperandInject{});
+}
+
+// the test hook's own instantiation: same packing, same MFMA, one xor between
+template <int DT>
+__global__ void mfma_exact_inject_kernel(float* __restrict__ out, uint32_t seed,
+                                         uint32_t wg_base, OperandInject inj) {
+  mfma_exact_body<DT, true>(out, seed, wg_base, inj);
 }
 
 struct MfmaStats {
@@ -657,9 +819,28 @@ __global__ void mfma_check_kernel(const float* __restrict__ d, int dtype,
   }
 }
 
+template <int DT>
+static void launch_mfma_exact_inject(float* d_out, const dim3& grid, uint32_t seed,
+                                     uint32_t wg_base, const OperandInject& inj) {
+  hipLaunchKernelGGL(mfma_exact_inject_kernel<DT>, grid, dim3(64), 0, 0, d_out, seed,
+                     wg_base, inj);
+}
+
+// inject == nullptr launches the production kernels
 static void launch_mfma_exact(int dtype, float* d_out, int workgroups,
-                              uint32_t seed, uint32_t wg_base) {
+                              uint32_t seed, uint32_t wg_base,
+                              const OperandInject* inject = nullptr) {
   const dim3 grid(workgroups), block(64);
+  if (inject) {
+    switch (dtype) {
+      case gh::BF16: launch_mfma_exact_inject<gh::BF16>(d_out, grid, seed, wg_base, *inject); break;
+      case gh::F16: launch_mfma_exact_inject<gh::F16>(d_out, grid, seed, wg_base, *inject); break;
+      case gh::FP8: launch_mfma_exact_inject<gh::FP8>(d_out, grid, seed, wg_base, *inject); break;
+      default: launch_mfma_exact_inject<gh::MXFP4>(d_out, grid, seed, wg_base, *inject); break;
+    }
+    HIP_CHECK(hipGetLastError());
+    return;
+  }
   switch (dtype) {
     case gh::BF16:
       hipLaunchKernelGGL(mfma_exact_kernel<gh::BF16>, grid, block, 0, 0, d_out, seed, wg_base);
@@ -684,14 +865,31 @@ struct MfmaResult {
   float got = 0.f, expected = 0.f;
 };
 
+// what of an operand injection depends on the data type and on the launch
+static void check_operand_inject(const OperandInject& inj, int dtype, int workgroups) {
+  if (inj.wg >= (uint32_t)workgroups)
+    throw py::value_error("injected workgroup is outside the launch");
+  if ((inj.operand == OP_SA || inj.operand == OP_SB) && dtype != gh::MXFP4)
+    throw py::value_error("only mxfp4 has the scale operands sa and sb");
+  const uint32_t regs = inj.operand == OP_C ? 4u
+                        : (inj.operand == OP_A || inj.operand == OP_B)
+                            ? (uint32_t)operand_dwords(dtype) : 1u;
+  if (inj.reg >= regs)
+    throw py::value_error("injected register is outside the operand's " +
+                          std::to_string(regs) + " dwords");
+}
+
 // corruptions: the host xors each mask into that element of D
 // ((workgroup * 16 + row) * 16 + col) between the MFMA pass and the check.
+// inject: an operand-side fault, applied by the kernel before the MFMA.
 static MfmaResult run_mfma_verify(int dtype, int workgroups, uint32_t seed,
-                                  corruptions_t corruptions = {}) {
+                                  corruptions_t corruptions = {},
+                                  const OperandInject* inject = nullptr) {
   if (workgroups < 1 || workgroups > (1 << 20))
     throw py::value_error("workgroups must be in [1, 2^20]");
   const size_t n = (size_t)workgroups * 256;
   corruptions = checked_corruptions(std::move(corruptions), n, "corrupted element");
+  if (inject) check_operand_inject(*inject, dtype, workgroups);
 
   DeviceScope scope;
   float* d_out = (float*)scope.alloc(n * sizeof(float));
@@ -699,7 +897,7 @@ static MfmaResult run_mfma_verify(int dtype, int workgroups, uint32_t seed,
   MfmaStats st{0, kNoBadWord};
   HIP_CHECK(hipMemcpy(d_stats, &st, sizeof(st), hipMemcpyHostToDevice));
 
-  launch_mfma_exact(dtype, d_out, workgroups, seed, 0);
+  launch_mfma_exact(dtype, d_out, workgroups, seed, 0, inject);
   for (const auto& [element, mask] : corruptions)
     xor_device_word(d_out + element, (uint32_t)mask);
   hipLaunchKernelGGL(mfma_check_kernel, dim3(workgroups), dim3(64), 0, 0,
@@ -722,14 +920,16 @@ static MfmaResult run_mfma_verify(int dtype, int workgroups, uint32_t seed,
 }
 
 // test hook: the raw fp32 D buffer of the production MFMA pass
-static std::string run_debug_mfma_dump(int dtype, int workgroups, uint32_t seed) {
+static std::string run_debug_mfma_dump(int dtype, int workgroups, uint32_t seed,
+                                       const OperandInject* inject = nullptr) {
   if (workgroups < 1 || workgroups > 4096)
     throw py::value_error("workgroups must be in [1, 4096]");
+  if (inject) check_operand_inject(*inject, dtype, workgroups);
   const size_t bytes = (size_t)workgroups * 256 * sizeof(float);
   DeviceScope scope;
   float* d_out = (float*)scope.alloc(bytes);
   HIP_CHECK(hipMemset(d_out, 0xFF, bytes));  // an unwritten element reads as NaN
-  launch_mfma_exact(dtype, d_out, workgroups, seed, 0);
+  launch_mfma_exact(dtype, d_out, workgroups, seed, 0, inject);
   HIP_CHECK(hipDeviceSynchronize());
   std::string host(bytes, '\0');
   HIP_CHECK(hipMemcpy(&host[0], d_out, bytes, hipMemcpyDeviceToHost));
@@ -780,6 +980,8 @@ struct CuInject {
   uint32_t lds_on = 0, lds_visit = 0, lds_word = 0, lds_mask = 0, lds_phase = 0;
   uint32_t mfma_on = 0, mfma_visit = 0, mfma_wave = 0, mfma_dtype = 0,
            mfma_element = 0, mfma_mask = 0;
+  // stuck-at: forced after every fill of that visit, in all passes and phases
+  uint32_t stuck_on = 0, stuck_visit = 0, stuck_word = 0, stuck_mask = 0, stuck_value = 0;
 };
 
 __device__ inline uint32_t read_xcc_id_reg() {
@@ -870,6 +1072,13 @@ __global__ __launch_bounds__(kSweepThreads) void cu_sweep_kernel(
       __syncthreads();
       if (inj.lds_on && visit == inj.lds_visit && phase == inj.lds_phase && pass == 0) {
         if (threadIdx.x == 0) ((uint32_t*)lds_vec)[inj.lds_word] ^= inj.lds_mask;
+        __syncthreads();
+      }
+      if (inj.stuck_on && visit == inj.stuck_visit) {
+        if (threadIdx.x == 0) {
+          uint32_t* word = (uint32_t*)lds_vec + inj.stuck_word;
+          *word = forced_word(*word, inj.stuck_mask, inj.stuck_value);
+        }
         __syncthreads();
       }
       // 16-byte reads, the fill's own lane map
@@ -1026,6 +1235,12 @@ static CuSweepResult run_cu_sweep(uint32_t seed, int passes, uint64_t lds_bytes,
     if (inject.lds_word >= res.lds_bytes / 4)
       throw py::value_error("injected LDS word is outside the checked range");
   }
+  if (inject.stuck_on) {
+    if (inject.stuck_visit >= visits)
+      throw py::value_error("injected visit is outside [0, blocks_per_round x max_rounds)");
+    if (inject.stuck_word >= res.lds_bytes / 4)
+      throw py::value_error("stuck LDS word is outside the checked range");
+  }
   if (inject.mfma_on && inject.mfma_visit >= visits)
     throw py::value_error("injected visit is outside [0, blocks_per_round x max_rounds)");
   res.blocks_per_round = blocks_per_round;
@@ -1059,8 +1274,9 @@ static CuSweepResult run_cu_sweep(uint32_t seed, int passes, uint64_t lds_bytes,
   HIP_CHECK(hipEventElapsedTime(&ms, t0, t1));
   res.elapsed_ms = ms;
 
-  if (inject.lds_on || inject.mfma_on) {
-    const uint32_t visit = inject.lds_on ? inject.lds_visit : inject.mfma_visit;
+  if (inject.lds_on || inject.stuck_on || inject.mfma_on) {
+    const uint32_t visit = inject.lds_on ? inject.lds_visit
+                           : inject.stuck_on ? inject.stuck_visit : inject.mfma_visit;
     if (visit < (uint64_t)res.rounds * blocks_per_round) {
       HIP_CHECK(hipMemcpy(&res.record, d_records + visit, sizeof(CuRecord),
                           hipMemcpyDeviceToHost));
@@ -1169,7 +1385,7 @@ static py::dict hbm_pattern_check(int device, double mib, double fraction,
                                   int corrupt_bit, uint64_t bytes,
                                   uint64_t max_chunk_mib, int passes,
                                   uint64_t base_word, corruptions_t corruptions,
-                                  std::pair<int, int> corrupt_at) {
+                                  std::pair<int, int> corrupt_at, stuck_t stuck) {
   if (bytes == 0 && fraction == 0.0) {
     if (!(mib > 0.0)) throw py::value_error("mib must be positive");
     bytes = (uint64_t)(mib * 1048576.0) & ~(uint64_t)15;
@@ -1182,7 +1398,7 @@ static py::dict hbm_pattern_check(int device, double mib, double fraction,
   use_device(device);
   return pattern_dict(run_hbm_pattern(bytes, fraction, seed, passes, max_chunk_mib << 20,
                                       base_word, std::move(corruptions),
-                                      corrupt_at.first, corrupt_at.second));
+                                      corrupt_at.first, corrupt_at.second, std::move(stuck)));
 }
 
 static py::bytes debug_pattern_fill(int device, uint64_t bytes, uint32_t seed,
@@ -1214,21 +1430,46 @@ static py::dict mfma_dict(const MfmaResult& r) {
 
 // corrupt_element >= 0 is shorthand for corruptions = [(corrupt_element,
 // 1 << 20)], one mantissa bit
+// (workgroup, lane, operand, reg, mask); what depends on the data type and the
+// launch is checked by check_operand_inject
+typedef std::optional<std::tuple<int64_t, int64_t, std::string, int64_t, int64_t>>
+    inject_operand_t;
+
+static std::optional<OperandInject> checked_operand_inject(const inject_operand_t& in) {
+  if (!in) return std::nullopt;
+  const auto& [wg, lane, operand, reg, mask] = *in;
+  static const char* const kNames[] = {"a", "b", "c", "sa", "sb"};
+  OperandInject inj;
+  inj.operand = 5;
+  for (uint32_t n = 0; n < 5; ++n)
+    if (operand == kNames[n]) inj.operand = n;
+  if (inj.operand == 5)
+    throw py::value_error("operand must be one of a, b, c, sa, sb (got '" + operand + "')");
+  inj.wg = checked_index(wg, 1ull << 20, "injected workgroup");
+  inj.lane = checked_index(lane, 64, "injected lane");
+  inj.reg = checked_index(reg, 8, "injected register");
+  inj.mask = checked_mask(mask);
+  return inj;
+}
+
 static py::dict mfma_verify(int device, const std::string& dtype, int workgroups,
                             uint32_t seed, int64_t corrupt_element,
-                            corruptions_t corruptions) {
+                            corruptions_t corruptions, inject_operand_t inject_operand) {
   const int dt = parse_dtype(dtype);
   if (corrupt_element < -1) throw py::value_error("corrupt_element is outside the output buffer");
   if (corrupt_element >= 0) corruptions.emplace_back(corrupt_element, (int64_t)1 << 20);
+  const std::optional<OperandInject> inj = checked_operand_inject(inject_operand);
   use_device(device);
-  return mfma_dict(run_mfma_verify(dt, workgroups, seed, std::move(corruptions)));
+  return mfma_dict(run_mfma_verify(dt, workgroups, seed, std::move(corruptions),
+                                   inj ? &*inj : nullptr));
 }
 
 static py::bytes debug_mfma_dump(int device, const std::string& dtype, int workgroups,
-                                 uint32_t seed) {
+                                 uint32_t seed, inject_operand_t inject_operand) {
   const int dt = parse_dtype(dtype);
+  const std::optional<OperandInject> inj = checked_operand_inject(inject_operand);
   use_device(device);
-  return py::bytes(run_debug_mfma_dump(dt, workgroups, seed));
+  return py::bytes(run_debug_mfma_dump(dt, workgroups, seed, inj ? &*inj : nullptr));
 }
 
 typedef std::vector<std::vector<float>> matrix_t;
@@ -1274,21 +1515,21 @@ static const char* const kDtypeNames[gh::kNumDtypes] = {"bf16", "f16", "fp8", "m
 typedef std::optional<std::tuple<int64_t, int64_t, int64_t, int64_t>> inject_lds_t;
 typedef std::optional<std::tuple<int64_t, int64_t, std::string, int64_t, int64_t>> inject_mfma_t;
 
-static uint32_t checked_mask(int64_t mask) {
-  if (mask <= 0 || mask > 0xFFFFFFFFll)
-    throw py::value_error("xor mask must be a non-zero 32-bit value");
-  return (uint32_t)mask;
-}
-
-static uint32_t checked_index(int64_t v, uint64_t limit, const char* what) {
-  if (v < 0 || (uint64_t)v >= limit)
-    throw py::value_error(std::string(what) + " is outside the checked range");
-  return (uint32_t)v;
-}
-
 // everything that does not depend on the device; run_cu_sweep checks the rest
-static CuInject checked_inject(const inject_lds_t& lds, const inject_mfma_t& mfma) {
+static CuInject checked_inject(const inject_lds_t& lds, const inject_mfma_t& mfma,
+                               const inject_lds_t& stuck) {
   CuInject inj;
+  if (lds && stuck)
+    throw py::value_error("inject_lds and inject_lds_stuck cannot be combined");
+  if (stuck) {
+    const auto& [visit, word, mask, value] = *stuck;
+    inj.stuck_on = 1;
+    inj.stuck_visit = checked_index(visit, kSweepMaxVisits, "injected visit");
+    inj.stuck_word = checked_index(word, 1ull << 30, "stuck LDS word");
+    inj.stuck_mask = checked_mask(mask);
+    if (value != 0 && value != 1) throw py::value_error("stuck value must be 0 or 1");
+    inj.stuck_value = (uint32_t)value;
+  }
   if (lds) {
     const auto& [visit, word, mask, phase] = *lds;
     inj.lds_on = 1;
@@ -1308,6 +1549,8 @@ static CuInject checked_inject(const inject_lds_t& lds, const inject_mfma_t& mfm
   }
   if (lds && mfma && inj.lds_visit != inj.mfma_visit)
     throw py::value_error("inject_lds and inject_mfma must name the same visit");
+  if (stuck && mfma && inj.stuck_visit != inj.mfma_visit)
+    throw py::value_error("inject_lds_stuck and inject_mfma must name the same visit");
   return inj;
 }
 
@@ -1403,11 +1646,11 @@ static py::dict cu_sweep_dict(const CuSweepResult& r, bool injected) {
 
 static py::dict cu_sweep(int device, uint32_t seed, int passes, uint64_t lds_bytes,
                          int blocks_per_round, int max_rounds, inject_lds_t inject_lds,
-                         inject_mfma_t inject_mfma) {
-  const CuInject inj = checked_inject(inject_lds, inject_mfma);
+                         inject_mfma_t inject_mfma, inject_lds_t inject_lds_stuck) {
+  const CuInject inj = checked_inject(inject_lds, inject_mfma, inject_lds_stuck);
   use_device(device);
   return cu_sweep_dict(run_cu_sweep(seed, passes, lds_bytes, blocks_per_round, max_rounds, inj),
-                       inj.lds_on || inj.mfma_on);
+                       inj.lds_on || inj.stuck_on || inj.mfma_on);
 }
 
 static py::dict decode_location_py(uint32_t xcc_id_reg, uint32_t hw_id_reg) {
@@ -1469,10 +1712,11 @@ PYBIND11_MODULE(gpuhealth, m) {
         py::arg("corrupt_bit") = 0, py::arg("bytes") = 0,
         py::arg("max_chunk_mib") = 16384, py::arg("passes") = 1,
         py::arg("base_word") = 0, py::arg("corruptions") = corruptions_t{},
-        py::arg("corrupt_at") = std::pair<int, int>(0, 0));
+        py::arg("corrupt_at") = std::pair<int, int>(0, 0), py::arg("stuck") = stuck_t{});
   m.def("mfma_verify", &mfma_verify, py::arg("device") = 0, py::arg("dtype") = "bf16",
         py::arg("workgroups") = 1024, py::arg("seed") = gh::kDefaultSeed,
-        py::arg("corrupt_element") = -1, py::arg("corruptions") = corruptions_t{});
+        py::arg("corrupt_element") = -1, py::arg("corruptions") = corruptions_t{},
+        py::arg("inject_operand") = py::none());
   // test hooks: the production kernels through the production launch code,
   // with what they wrote handed back
   m.def("debug_pattern_fill", &debug_pattern_fill, py::arg("device") = 0,
@@ -1482,7 +1726,7 @@ PYBIND11_MODULE(gpuhealth, m) {
         py::arg("bytes") = 4096, py::arg("seed") = gh::kDefaultSeed);
   m.def("debug_mfma_dump", &debug_mfma_dump, py::arg("device") = 0,
         py::arg("dtype") = "bf16", py::arg("workgroups") = 64,
-        py::arg("seed") = gh::kDefaultSeed);
+        py::arg("seed") = gh::kDefaultSeed, py::arg("inject_operand") = py::none());
   m.def("mfma_verify_tile", &mfma_verify_tile, py::arg("device") = 0,
         py::arg("dtype") = "bf16", py::arg("seed") = gh::kDefaultSeed,
         py::arg("workgroup") = 0);
@@ -1491,7 +1735,7 @@ PYBIND11_MODULE(gpuhealth, m) {
   m.def("cu_sweep", &cu_sweep, py::arg("device") = 0, py::arg("seed") = gh::kDefaultSeed,
         py::arg("passes") = 1, py::arg("lds_bytes") = 0, py::arg("blocks_per_round") = 0,
         py::arg("max_rounds") = 8, py::arg("inject_lds") = py::none(),
-        py::arg("inject_mfma") = py::none());
+        py::arg("inject_mfma") = py::none(), py::arg("inject_lds_stuck") = py::none());
   m.def("decode_location", &decode_location_py, py::arg("xcc_id_reg"), py::arg("hw_id_reg"));
   m.def("debug_cu_lds_dump", &debug_cu_lds_dump, py::arg("device") = 0,
         py::arg("lds_bytes") = 0, py::arg("seed") = gh::kDefaultSeed,

@@ -19,6 +19,17 @@
 // stuck-at-0 fault on those operand bits is outside what the data can show.
 // Every other operand bit, every e2m1 bit and every E8M0 scale bit takes both
 // values (tests/test_gpu_probe_kernels.py).
+//
+// Shown on the device with seeded faults that enter on the input side
+// (tests/test_gpu_input_faults.py): an xor into one operand register of one
+// lane before the MFMA changes D exactly as the operand lane maps say, for A,
+// B, C and the MX scales, the low mantissa bits and a non-finite operand
+// included, and the check flags it; the MX instruction ignores bytes 1..3 of a
+// scale register and VGPRs 4..7 of the eight-VGPR FP4 operand; a stuck-at bit
+// in the HBM sweep and in the LDS march is reported in exactly one of the two
+// phases of every pass, whichever value it is stuck at. Still not shown:
+// subnormal operands, and a stuck-at-0 on the low mantissa bits: the test
+// flips them, the production data never sets them.
 #pragma once
 
 #include <cstdint>

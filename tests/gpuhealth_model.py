@@ -210,8 +210,13 @@ DECODE = {"bf16": bf16_to_f32, "f16": f16_to_f32, "fp8": e4m3_to_f32}
 #                      B operand = B[8g + j][i]
 #   mxfp4            : 16 operand bytes; nibble j (0..31) is k = 32g + j, the
 #                      even element in the low nibble of byte j // 2; scale
-#                      byte sa = E8M0(row i, block g), sb = E8M0(col i, block g)
+#                      byte sa = E8M0(row i, block g), sb = E8M0(col i, block g).
+#                      The operand is eight VGPRs wide and the scale register
+#                      four bytes: bytes 16..31 of the one and bytes 1..3 of
+#                      the other are ignored
 #   C / D            : register r (0..3) = [4g + r][i]
+# xor_register applies a seeded operand fault to these registers, dword by
+# dword as the kernel's inject_operand hook does.
 # ---------------------------------------------------------------------------
 FAULTS_ALL = ("swap_k_groups", "swap_rows", "reverse_j", "reverse_c", "reverse_d",
               "transpose_d")
@@ -220,15 +225,18 @@ FAULTS_MXFP4 = ("swap_nibbles", "scale_other_block", "swap_scales")
 
 def pack_registers(dtype, seed, wg):
     """Per-lane registers as the kernel builds them: 'a' and 'b' are
-    [64][8] element codes (bf16 / f16 / fp8) or [64][16] bytes (mxfp4), 'sa'
-    and 'sb' [64] E8M0 bytes (mxfp4 only), 'c' [64][4] values."""
+    [64][8] element codes (bf16 / f16 / fp8) or [64][32] bytes (mxfp4: the
+    eight VGPRs of the operand, FP4 data in the first 16 bytes and zeros in
+    VGPRs 4..7), 'sa' and 'sb' [64] 32-bit scale registers with the E8M0 in
+    byte 0 (mxfp4 only), 'c' [64][4] values."""
     regs = {"a": [], "b": [], "sa": [], "sb": [], "c": []}
     for lane in range(64):
         i, g = lane & 15, lane >> 4
         if dtype == "mxfp4":
             for name, which in (("a", GEN_A), ("b", GEN_B)):
                 codes = [gen_fp4_code(seed, wg, which, i, 32 * g + j) for j in range(32)]
-                regs[name].append([codes[2 * n] | (codes[2 * n + 1] << 4) for n in range(16)])
+                regs[name].append([codes[2 * n] | (codes[2 * n + 1] << 4) for n in range(16)]
+                                  + [0] * 16)
             regs["sa"].append(gen_scale_code(seed, wg, GEN_SA, i, g))
             regs["sb"].append(gen_scale_code(seed, wg, GEN_SB, i, g))
         else:
@@ -241,12 +249,64 @@ def pack_registers(dtype, seed, wg):
     return regs
 
 
+OPERANDS = ("a", "b", "c", "sa", "sb")
+
+
+def operand_dwords(dtype, operand):
+    """32-bit registers one lane holds of that operand."""
+    if operand in ("sa", "sb"):
+        return 1
+    if operand == "c":
+        return 4
+    return {"bf16": 4, "f16": 4, "fp8": 2, "mxfp4": 8}[dtype]
+
+
+def xor_register(dtype, regs, lane, operand, reg, mask):
+    """A copy of regs with the 32-bit mask xored into dword reg of that lane's
+    operand, little-endian: a 16-bit element 2 reg in the low half, bytes
+    4 reg .. 4 reg + 3 from the low byte up."""
+    assert operand in OPERANDS and 0 <= lane < 64 and 0 < mask <= M32
+    assert 0 <= reg < operand_dwords(dtype, operand)
+    assert dtype == "mxfp4" or operand not in ("sa", "sb")
+    out = {name: [list(v) if isinstance(v, list) else v for v in per_lane]
+           for name, per_lane in regs.items()}
+    if operand in ("sa", "sb"):
+        out[operand][lane] ^= mask
+    elif operand == "c":
+        out["c"][lane][reg] = bits_f32(f32_bits(out["c"][lane][reg]) ^ mask)
+    elif dtype in ("bf16", "f16"):
+        out[operand][lane][2 * reg] ^= mask & 0xFFFF
+        out[operand][lane][2 * reg + 1] ^= mask >> 16
+    else:
+        for n in range(4):
+            out[operand][lane][4 * reg + n] ^= (mask >> (8 * n)) & 0xFF
+    return out
+
+
+def _matmul_add(A, B, C_):
+    """A·B + C. Finite operands: numpy. A non-finite operand: products and
+    sums element by element in k order, so that where a NaN or an infinity
+    lands does not depend on a BLAS."""
+    if np.isfinite(A).all() and np.isfinite(B).all() and np.isfinite(C_).all():
+        return A @ B + C_
+    D = np.zeros((A.shape[0], B.shape[1]))
+    for r in range(A.shape[0]):
+        for c in range(B.shape[1]):
+            acc = float(C_[r, c])
+            for k in range(A.shape[1]):
+                acc += float(A[r, k]) * float(B[k, c])
+            D[r, c] = acc
+    return D
+
+
 def _lane_values(dtype, reg, swap_nibbles=False):
-    """The k-ordered element values one lane's operand register decodes to."""
+    """The k-ordered element values one lane's operand register decodes to.
+    Of the eight-VGPR FP4 operand only VGPRs 0..3 hold data: the instruction
+    ignores the rest."""
     if dtype != "mxfp4":
         return [DECODE[dtype](code) for code in reg]
     out = []
-    for byte in reg:
+    for byte in reg[:16]:
         even, odd = byte & 15, byte >> 4
         if swap_nibbles:
             even, odd = odd, even
@@ -254,11 +314,10 @@ def _lane_values(dtype, reg, swap_nibbles=False):
     return out
 
 
-def tile_from_registers(dtype, regs, fault=None):
-    """D (16 x 16, row-major as the kernel stores it) computed from the packed
-    registers. fault=None unpacks by the documented lane maps; a fault name
-    gets exactly one thing wrong, on the A side where a side has to be chosen
-    (the same mistake on both A and B would cancel in the dot product)."""
+def matrices_from_registers(dtype, regs, fault=None):
+    """Logical A (16 x K), B (K x 16) and C (16 x 16), float64, unpacked from
+    the registers; fault as in tile_from_registers (the D-side faults do not
+    act here)."""
     assert fault is None or fault in FAULTS_ALL + FAULTS_MXFP4
     K = k_of(dtype)
     per = K // 4
@@ -279,13 +338,22 @@ def tile_from_registers(dtype, regs, fault=None):
             sb = regs["sb"][lane]
             if fault == "swap_scales":
                 sa, sb = sb, sa
-            va = [v * e8m0_to_float(sa) for v in va]
-            vb = [v * e8m0_to_float(sb) for v in vb]
+            # opsel 0: the E8M0 is byte 0 of the scale register, the rest is ignored
+            va = [v * e8m0_to_float(sa & 0xFF) for v in va]
+            vb = [v * e8m0_to_float(sb & 0xFF) for v in vb]
         A[i, per * g:per * g + per] = va
         B[per * g:per * g + per, i] = vb
         c = regs["c"][lane]
         C_[4 * g:4 * g + 4, i] = c[::-1] if fault == "reverse_c" else c
-    D = A @ B + C_
+    return A, B, C_
+
+
+def tile_from_registers(dtype, regs, fault=None):
+    """D (16 x 16, row-major as the kernel stores it) computed from the packed
+    registers. fault=None unpacks by the documented lane maps; a fault name
+    gets exactly one thing wrong, on the A side where a side has to be chosen
+    (the same mistake on both A and B would cancel in the dot product)."""
+    D = _matmul_add(*matrices_from_registers(dtype, regs, fault))
     out = np.zeros((16, 16))
     for lane in range(64):
         i, g = lane & 15, lane >> 4

@@ -233,6 +233,17 @@ def test_bad_arguments_raise_and_leave_the_device_usable(native, lds_max):
         dict(small, inject_mfma=(0, 0, "bf16", -1, 1)),
         dict(small, inject_mfma=(0, 0, "bf16", 0, 0)),
         dict(small, inject_lds=(0, 0, 1, 0), inject_mfma=(1, 0, "bf16", 0, 1)),
+        dict(small, inject_lds_stuck=(-1, 0, 1, 0)), dict(small, inject_lds_stuck=(2, 0, 1, 0)),
+        dict(small, inject_lds_stuck=(0, n_words, 1, 0)),
+        dict(small, inject_lds_stuck=(0, -1, 1, 0)),
+        dict(small, lds_bytes=16, inject_lds_stuck=(0, 4, 1, 0)),
+        dict(small, inject_lds_stuck=(0, 0, 0, 0)),
+        dict(small, inject_lds_stuck=(0, 0, 1 << 32, 0)),
+        dict(small, inject_lds_stuck=(0, 0, -1, 0)), dict(small, inject_lds_stuck=(0, 0, 1, 2)),
+        dict(small, inject_lds_stuck=(0, 0, 1, -1)),
+        dict(small, inject_lds=(0, 0, 1, 0), inject_lds_stuck=(0, 0, 1, 0)),
+        dict(small, inject_lds=(0, 0, 1, 0), inject_lds_stuck=(0, 1, 1, 0)),
+        dict(small, inject_lds_stuck=(0, 0, 1, 0), inject_mfma=(1, 0, "bf16", 0, 1)),
     ]
     for kwargs in bad:
         with pytest.raises(ValueError):

@@ -323,6 +323,15 @@ def test_debug_hooks_reject_bad_arguments(native):
             native.debug_mfma_dump(0, "bf16", wgs)
     with pytest.raises(ValueError):
         native.debug_mfma_dump(0, "int8", 1)
+    for bad in ((0, 64, "a", 0, 1), (0, -1, "b", 0, 1), (0, 0, "a", 4, 1), (0, 0, "c", 4, 1),
+                (0, 0, "sb", 0, 1), (0, 0, "b", 0, 0), (0, 0, "b", 0, 1 << 32),
+                (1, 0, "a", 0, 1), (-1, 0, "a", 0, 1), (0, 0, "d", 0, 1)):
+        with pytest.raises(ValueError):
+            native.debug_mfma_dump(0, "bf16", 1, inject_operand=bad)
+    for dtype, bad in (("fp8", (0, 0, "a", 2, 1)), ("mxfp4", (0, 0, "a", 8, 1)),
+                       ("mxfp4", (0, 0, "sa", 1, 1))):
+        with pytest.raises(ValueError):
+            native.debug_mfma_dump(0, dtype, 1, inject_operand=bad)
 
 
 # ---------------------------------------------------------------------------
@@ -458,6 +467,16 @@ def test_corruption_arguments_are_checked(native):
         check(0, bytes=4096, passes=2, corruptions=[(3, 1)], corrupt_at=(2, 0))
     with pytest.raises(ValueError):
         check(0, bytes=4096, base_word=(1 << 64) - 1024)
+    for bad in ([(1024, 1, 0)], [(-1, 1, 0)], [(3, 0, 0)], [(3, 1 << 32, 1)], [(3, -1, 1)],
+                [(3, 1, 2)], [(3, 1, -1)], [(3, 1, 0), (3, 2, 1)]):
+        with pytest.raises(ValueError):
+            check(0, bytes=4096, stuck=bad)
+    with pytest.raises(ValueError):
+        check(0, bytes=4096, corruptions=[(3, 1)], stuck=[(5, 1, 0), (1024, 1, 0)])
+    for bad in ((0, 64, "a", 0, 1), (0, 0, "a", 4, 1), (0, 0, "sa", 0, 1), (0, 0, "a", 0, 0),
+                (0, 0, "a", 0, 1 << 32), (4, 0, "a", 0, 1), (0, 0, "e", 0, 1)):
+        with pytest.raises(ValueError):
+            native.mfma_verify(0, "bf16", workgroups=4, inject_operand=bad)
     for bad in ([(4 * 256, 1)], [(-1, 1)], [(3, 0)], [(3, 1 << 32)], [(3, 1), (3, 2)]):
         with pytest.raises(ValueError):
             native.mfma_verify(0, "bf16", workgroups=4, corruptions=bad)

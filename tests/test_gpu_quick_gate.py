@@ -318,6 +318,17 @@ def _device_bindings(native):
         "debug_pattern_fill": lambda d: native.debug_pattern_fill(d, 4096),
         "debug_stream_copy_check": lambda d: native.debug_stream_copy_check(d, 4096),
         "mfma_verify_tile": lambda d: native.mfma_verify_tile(d, "bf16"),
+        "cu_sweep": lambda d: native.cu_sweep(d, blocks_per_round=1, max_rounds=1),
+        "debug_cu_lds_dump": lambda d: native.debug_cu_lds_dump(d, 16),
+        # the same bindings through their input-side fault hooks
+        "hbm_pattern_check(stuck)": lambda d: native.hbm_pattern_check(
+            d, bytes=4096, stuck=[(3, 1, 0)]),
+        "mfma_verify(inject_operand)": lambda d: native.mfma_verify(
+            d, "bf16", workgroups=4, inject_operand=(0, 0, "a", 0, 1)),
+        "debug_mfma_dump(inject_operand)": lambda d: native.debug_mfma_dump(
+            d, "bf16", 4, inject_operand=(0, 0, "a", 0, 1)),
+        "cu_sweep(inject_lds_stuck)": lambda d: native.cu_sweep(
+            d, blocks_per_round=1, max_rounds=1, inject_lds_stuck=(0, 0, 1, 0)),
     }
 
 
