@@ -89,6 +89,42 @@
 //                    after every fill of one visit: a stuck bit is reported by
 //                    both verifies in exactly one phase of every pass, which
 //                    shows the march's own inversion and that every pass runs.
+//   * mfma_load    — opt-in (seconds, on request only): the checks above give
+//                    right answers once, within a millisecond, at the idle
+//                    clock. This one keeps all four matrix pipes of every CU
+//                    busy for seconds and stays exactly checkable: a wave
+//                    holds A, B and C of an exact tile and issues
+//                    acc = mfma(A, B, acc), acc = mfma(-A, B, acc), ...
+//                    (alternating-sign premise, gpuhealth_ref.hpp), so acc is
+//                    C + A·B after an odd count and C after an even one, and
+//                    every partial sum is exact in fp32. Workgroups of four
+//                    waves, one per SIMD, that take the whole LDS of a CU; a
+//                    wave keeps four independent chains going, compares them
+//                    every check_every MFMAs (odd) with expectations computed
+//                    off the matrix pipe and starts again from C; it stamps
+//                    s_memtime and s_memrealtime around the loop. Launches of
+//                    about 50 ms, sized by a first short one, go back to back
+//                    (two in flight) until the time asked for is over; no
+//                    workgroup waits on another and no kernel on a clock.
+//                    Proves: for the time it ran, every matrix pipe of every
+//                    covered CU gave exact sums under sustained load (a fault
+//                    is named by XCC/SE/SH/CU, SIMD and data type), and the
+//                    device sustained floor_tflops. Reports the clock the
+//                    waves saw (Δmemtime ÷ Δmemrealtime × 100 MHz) and the
+//                    cycles per MFMA, so a low rate can be told apart: a
+//                    parked clock shows in the one, a stalled pipe in the
+//                    other; the slowest CU is reported, never gating. Cannot
+//                    show: an error that enters the accumulator below one
+//                    unit of the data (1, or 1/16 for MXFP4) can be rounded
+//                    away before the next check, check_every bounds that
+//                    window; the operands' low mantissa bits are still never
+//                    set; CUs the dispatcher never handed over are not
+//                    covered (cu_covered says how many were). No HBM or LDS
+//                    traffic is mixed in. Test hooks: mfma_load(inject_acc=),
+//                    an xor into one accumulator register of lane 0 after a
+//                    named MFMA of a named chunk (its own instantiation), and
+//                    debug_mfma_load_dump (the accumulators of one workgroup
+//                    after exactly n MFMAs, through the production loop).
 //
 // What must agree between host and device (pattern, generators, encoders,
 // reference) is in gpuhealth_ref.hpp.
@@ -672,14 +708,33 @@ __device__ inline void xor_dword(V& v, uint32_t reg, uint32_t mask) {
   for (uint32_t r = 0; r < (uint32_t)N; ++r) v[r] ^= (r == reg ? mask : 0u);
 }
 
+// The packed A and B of one exact tile as one lane holds them (MXFP4: with the
+// two scale registers), kept apart from the MFMA so that a caller can hold on
+// to them, negate A and issue again (mfma_load_kernel).
+template <int DT> struct ExactOperands {
+  frag_ab_t a, b;
+};
+template <> struct ExactOperands<gh::F16> {
+  frag_f16_t a, b;
+};
+template <> struct ExactOperands<gh::FP8> {
+  uint64_t a, b;
+};
+template <> struct ExactOperands<gh::MXFP4> {
+  frag_i32x8_t a, b;
+  int sa, sb;
+};
+
 // inj_mask is zero in every lane but the injected one
 template <int DT, bool INJECT = false>
-__device__ inline frag_cd_t mfma_exact_tile(uint32_t seed, uint32_t wg, int lane,
-                                            frag_cd_t acc, uint32_t inj_operand = 0,
-                                            uint32_t inj_reg = 0, uint32_t inj_mask = 0) {
+__device__ inline ExactOperands<DT> pack_exact_operands(uint32_t seed, uint32_t wg, int lane,
+                                                        uint32_t inj_operand = 0,
+                                                        uint32_t inj_reg = 0,
+                                                        uint32_t inj_mask = 0) {
   const uint32_t i = lane & 15, g = lane >> 4;
   const uint32_t mask_a = inj_operand == OP_A ? inj_mask : 0u;
   const uint32_t mask_b = inj_operand == OP_B ? inj_mask : 0u;
+  ExactOperands<DT> op;
   if constexpr (DT == gh::BF16) {
     frag_ab_t a, b;
     for (uint32_t j = 0; j < 8; ++j) {
@@ -696,7 +751,8 @@ __device__ inline frag_cd_t mfma_exact_tile(uint32_t seed, uint32_t wg, int lane
       a = __builtin_bit_cast(frag_ab_t, ua);
       b = __builtin_bit_cast(frag_ab_t, ub);
     }
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, acc, 0, 0, 0);
+    op.a = a;
+    op.b = b;
   } else if constexpr (DT == gh::F16) {
     frag_f16_t a, b;
     for (uint32_t j = 0; j < 8; ++j) {
@@ -713,7 +769,8 @@ __device__ inline frag_cd_t mfma_exact_tile(uint32_t seed, uint32_t wg, int lane
       a = __builtin_bit_cast(frag_f16_t, ua);
       b = __builtin_bit_cast(frag_f16_t, ub);
     }
-    return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, acc, 0, 0, 0);
+    op.a = a;
+    op.b = b;
   } else if constexpr (DT == gh::FP8) {
     uint64_t a = 0, b = 0;
     for (uint32_t j = 0; j < 8; ++j) {
@@ -726,7 +783,8 @@ __device__ inline frag_cd_t mfma_exact_tile(uint32_t seed, uint32_t wg, int lane
       a ^= (uint64_t)mask_a << (32 * (inj_reg & 1u));
       b ^= (uint64_t)mask_b << (32 * (inj_reg & 1u));
     }
-    return __builtin_amdgcn_mfma_f32_16x16x32_fp8_fp8((long)a, (long)b, acc, 0, 0, 0);
+    op.a = a;
+    op.b = b;
   } else {
     frag_i32x8_t a = {0, 0, 0, 0, 0, 0, 0, 0}, b = {0, 0, 0, 0, 0, 0, 0, 0};
     for (uint32_t v = 0; v < 4; ++v) {
@@ -747,10 +805,54 @@ __device__ inline frag_cd_t mfma_exact_tile(uint32_t seed, uint32_t wg, int lane
       sa ^= (int)(inj_operand == OP_SA ? inj_mask : 0u);
       sb ^= (int)(inj_operand == OP_SB ? inj_mask : 0u);
     }
+    op.a = a;
+    op.b = b;
+    op.sa = sa;
+    op.sb = sb;
+  }
+  return op;
+}
+
+// acc = A·B + acc on the matrix pipe of this wave's SIMD
+template <int DT>
+__device__ inline frag_cd_t issue_exact_mfma(const ExactOperands<DT>& op, frag_cd_t acc) {
+  if constexpr (DT == gh::BF16) {
+    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(op.a, op.b, acc, 0, 0, 0);
+  } else if constexpr (DT == gh::F16) {
+    return __builtin_amdgcn_mfma_f32_16x16x32_f16(op.a, op.b, acc, 0, 0, 0);
+  } else if constexpr (DT == gh::FP8) {
+    return __builtin_amdgcn_mfma_f32_16x16x32_fp8_fp8((long)op.a, (long)op.b, acc, 0, 0, 0);
+  } else {
     // cbsz=4 / blgp=4: FP4 A and B, which the instruction takes from VGPRs 0..3
     // of each eight-VGPR operand; opsel 0: the scale is byte 0 of its register
-    return __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(a, b, acc, 4, 4, 0, sa, 0, sb);
+    return __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(op.a, op.b, acc, 4, 4, 0, op.sa, 0,
+                                                            op.sb);
   }
+}
+
+// the same operands with every element of A negated (gh::negate_mask); of the
+// eight-VGPR FP4 operand only VGPRs 0..3 hold data
+template <int DT>
+__device__ inline ExactOperands<DT> negated_a(ExactOperands<DT> op) {
+  const uint32_t m = gh::negate_mask(DT);
+  if constexpr (DT == gh::BF16 || DT == gh::F16) {
+    frag_u32x4_t ua = __builtin_bit_cast(frag_u32x4_t, op.a);
+    for (int r = 0; r < 4; ++r) ua[r] ^= m;
+    op.a = __builtin_bit_cast(decltype(op.a), ua);
+  } else if constexpr (DT == gh::FP8) {
+    op.a ^= (uint64_t)m << 32 | m;
+  } else {
+    for (int r = 0; r < 4; ++r) op.a[r] ^= (int)m;
+  }
+  return op;
+}
+
+template <int DT, bool INJECT = false>
+__device__ inline frag_cd_t mfma_exact_tile(uint32_t seed, uint32_t wg, int lane,
+                                            frag_cd_t acc, uint32_t inj_operand = 0,
+                                            uint32_t inj_reg = 0, uint32_t inj_mask = 0) {
+  return issue_exact_mfma<DT>(
+      pack_exact_operands<DT, INJECT>(seed, wg, lane, inj_operand, inj_reg, inj_mask), acc);
 }
 
 // one wave per workgroup; D tiles are row-major, tile wg at out + 256 * wg
@@ -1303,6 +1405,380 @@ static std::string run_debug_cu_lds_dump(uint64_t lds_bytes, uint32_t seed, bool
 }
 
 // ---------------------------------------------------------------------------
+// Burn-in, part 4: MFMA load — all four matrix pipes of every CU kept busy for
+// seconds on exact tiles, checked every check_every MFMAs, timed by the waves
+//
+// The chain and why it stays exact are in gpuhealth_ref.hpp (alternating-sign
+// premise). A workgroup is four waves, one per SIMD, and takes the whole LDS of
+// its CU as the sweep does; a wave keeps kLoadTiles independent chains going.
+// No workgroup waits on another and no kernel waits on a clock: a launch is
+// bounded by n_mfmas x chunks alone.
+// ---------------------------------------------------------------------------
+constexpr int kLoadWaves = (int)gh::kLoadWaves;
+constexpr int kLoadTiles = (int)gh::kLoadTiles;
+constexpr int kLoadThreads = 64 * kLoadWaves;
+// +A / -A pairs per trip of the inner loop: 64 MFMAs. With one wave per SIMD
+// nothing hides the loop's branch, some 19 cycles a trip; at one pair (8
+// MFMAs, 128 cycles) per trip that is 15 %, at eight pairs under 2 %.
+constexpr uint32_t kLoadUnroll = 8;
+
+struct LoadSlot {
+  unsigned int visits;
+  unsigned int simd_seen;  // bit s: a wave of some visit ran on SIMD s
+  unsigned int bad[gh::kNumSimds];  // D elements that failed a check, by SIMD
+  // sums over the waves that ran here: s_memtime and s_memrealtime around the
+  // loop, and the MFMAs issued inside it
+  unsigned long long cycles, ticks, mfmas;
+};
+
+// where the workgroup of the injected visit ran (INJECT instantiation only)
+struct LoadRecord {
+  unsigned int written, key;
+  unsigned int simd[kLoadWaves];
+};
+
+// Test hook: an xor into one accumulator register of lane 0, applied after
+// MFMA number `after` (0-based, of that tile) of chunk `chunk`.
+struct LoadInject {
+  uint32_t visit = 0, wave = 0, tile = 0, chunk = 0, after = 0, reg = 0, mask = 0;
+};
+
+// mask is zero everywhere but in the lane, chunk and MFMA the hook names
+__device__ inline void xor_accumulator(frag_cd_t (&acc)[kLoadTiles], uint32_t tile,
+                                       uint32_t reg, uint32_t mask) {
+#pragma unroll
+  for (uint32_t t = 0; t < (uint32_t)kLoadTiles; ++t)
+    for (uint32_t r = 0; r < 4; ++r)
+      if (t == tile && r == reg) acc[t][r] = gh::bits_f32(gh::f32_bits(acc[t][r]) ^ mask);
+}
+
+// n_mfmas per tile and chunk: the production host passes an odd number, so a
+// chunk ends on C + A·B; the dump hook passes any. dump (DUMP only) receives
+// the accumulators as the last chunk left them, tile (wave, t) row-major at
+// dump + 256 * (kLoadTiles * wave + t).
+template <int DT, bool INJECT = false, bool DUMP = false>
+__global__ __launch_bounds__(kLoadThreads) void mfma_load_kernel(
+    LoadSlot* __restrict__ slots, uint32_t visit_base, uint32_t seed, uint32_t n_mfmas,
+    uint32_t chunks, LoadInject inj, LoadRecord* __restrict__ record,
+    float* __restrict__ dump) {
+  const int lane = threadIdx.x & 63;
+  const uint32_t wave = threadIdx.x >> 6;
+  const uint32_t visit = visit_base + blockIdx.x;
+  const uint32_t col = lane & 15, row0 = 4 * (lane >> 4);
+
+  const uint32_t xcc_reg = read_xcc_id_reg(), hw_reg = read_hw_id_reg();
+  const gh::CuLocation loc = gh::decode_location(xcc_reg, hw_reg);
+  const uint32_t key = gh::location_key(loc);
+  LoadSlot* slot = slots + key;
+
+  // operands and both expectations, once per operand set; the expectation is
+  // integer arithmetic over the generators, off the matrix pipe
+  ExactOperands<DT> pos[kLoadTiles], neg[kLoadTiles];
+  frag_cd_t c0[kLoadTiles], want[kLoadTiles], acc[kLoadTiles];
+#pragma unroll
+  for (int t = 0; t < kLoadTiles; ++t) {
+    const uint32_t wg = gh::load_tile_index(visit, wave, (uint32_t)t);
+    pos[t] = pack_exact_operands<DT>(seed, wg, lane);
+    neg[t] = negated_a<DT>(pos[t]);
+    for (uint32_t r = 0; r < 4; ++r) {
+      c0[t][r] = gh::expected_after(DT, seed, wg, row0 + r, col, 0);
+      want[t][r] = gh::expected_after(DT, seed, wg, row0 + r, col, n_mfmas);
+    }
+  }
+
+  const uint32_t pairs = (n_mfmas - 1) / 2;
+  const bool tail = ((n_mfmas - 1) & 1u) != 0;
+  [[maybe_unused]] const bool inj_here =
+      INJECT && visit == inj.visit && wave == inj.wave && lane == 0;
+  unsigned int bad = 0;
+
+  const uint64_t cycles0 = __builtin_amdgcn_s_memtime();
+  const uint64_t ticks0 = __builtin_amdgcn_s_memrealtime();
+  __builtin_amdgcn_sched_barrier(0);
+  for (uint32_t chunk = 0; chunk < chunks; ++chunk) {
+    [[maybe_unused]] const bool inj_chunk = inj_here && chunk == inj.chunk;
+    // acc = C again; opaque, so that no MFMA of a chunk is loop-invariant
+#pragma unroll
+    for (int t = 0; t < kLoadTiles; ++t) {
+      acc[t] = c0[t];
+      asm volatile("" : "+v"(acc[t]));
+    }
+#pragma unroll
+    for (int t = 0; t < kLoadTiles; ++t) acc[t] = issue_exact_mfma<DT>(pos[t], acc[t]);
+    if constexpr (INJECT)
+      xor_accumulator(acc, inj.tile, inj.reg, inj_chunk && inj.after == 0 ? inj.mask : 0u);
+    auto pair = [&](uint32_t p) {
+#pragma unroll
+      for (int t = 0; t < kLoadTiles; ++t) acc[t] = issue_exact_mfma<DT>(neg[t], acc[t]);
+      if constexpr (INJECT)
+        xor_accumulator(acc, inj.tile, inj.reg,
+                        inj_chunk && inj.after == 2 * p + 1 ? inj.mask : 0u);
+#pragma unroll
+      for (int t = 0; t < kLoadTiles; ++t) acc[t] = issue_exact_mfma<DT>(pos[t], acc[t]);
+      if constexpr (INJECT)
+        xor_accumulator(acc, inj.tile, inj.reg,
+                        inj_chunk && inj.after == 2 * p + 2 ? inj.mask : 0u);
+    };
+    // one wave per SIMD: nothing hides the loop branch, so it is paid once per
+    // kLoadUnroll pairs (64 MFMAs) and not once per pair. Unrolled by hand: the
+    // compiler does not unroll a loop of MFMAs with a run-time trip count.
+    uint32_t p = 0;
+    for (; p + kLoadUnroll <= pairs; p += kLoadUnroll) {
+#pragma unroll
+      for (uint32_t u = 0; u < kLoadUnroll; ++u) pair(p + u);
+    }
+    for (; p < pairs; ++p) pair(p);
+    if (tail) {
+#pragma unroll
+      for (int t = 0; t < kLoadTiles; ++t) acc[t] = issue_exact_mfma<DT>(neg[t], acc[t]);
+      if constexpr (INJECT)
+        xor_accumulator(acc, inj.tile, inj.reg,
+                        inj_chunk && inj.after == n_mfmas - 1 ? inj.mask : 0u);
+    }
+    // the compare of one tile runs under the last MFMAs of the others
+#pragma unroll
+    for (int t = 0; t < kLoadTiles; ++t)
+      for (uint32_t r = 0; r < 4; ++r) bad += !(acc[t][r] == want[t][r]);
+  }
+  __builtin_amdgcn_sched_barrier(0);
+  const uint64_t cycles1 = __builtin_amdgcn_s_memtime();
+  const uint64_t ticks1 = __builtin_amdgcn_s_memrealtime();
+
+  if constexpr (DUMP) {
+#pragma unroll
+    for (int t = 0; t < kLoadTiles; ++t) {
+      float* tile = dump + 256 * (kLoadTiles * wave + t);
+      for (uint32_t r = 0; r < 4; ++r) tile[(row0 + r) * 16 + col] = acc[t][r];
+    }
+  }
+
+  // publish: wave reductions, then lane 0 alone
+  if (__ballot(bad != 0) != 0) {
+    const unsigned int wave_bad = (unsigned int)wave_sum_u64(bad);
+    if (lane == 0) atomicAdd(&slot->bad[loc.simd], wave_bad);
+  }
+  if (lane != 0) return;
+  atomicOr(&slot->simd_seen, 1u << loc.simd);
+  atomicAdd(&slot->cycles, (unsigned long long)(cycles1 - cycles0));
+  atomicAdd(&slot->ticks, (unsigned long long)(ticks1 - ticks0));
+  atomicAdd(&slot->mfmas, (unsigned long long)kLoadTiles * n_mfmas * chunks);
+  if (wave == 0) atomicAdd(&slot->visits, 1u);
+  if constexpr (INJECT) {
+    if (visit == inj.visit) {
+      record->simd[wave] = loc.simd;
+      if (wave == 0) {
+        record->key = key;
+        record->written = 1;
+      }
+    }
+  }
+}
+
+// The smallest of 127, 143, ... 255 (steps of 16) whose TFLOP/s is within 3 %
+// of the rate at 4095 for every data type; fp8 decides (2346 against 2413; 223
+// gives 2339), bf16 alone would take 175, f16 159, MXFP4 127. And a launch
+// length at which the once-per-launch operand build costs 0.3 % (MXFP4 2.7 %)
+// (docs/benchmarks.md, "MFMA load").
+constexpr int kLoadDefaultCheckEvery = 239;
+constexpr double kLoadDefaultLaunchMs = 50.0;
+constexpr int kLoadMaxCheckEvery = 4095;
+constexpr int kLoadMaxBlocks = 1 << 14;
+constexpr double kLoadMaxSeconds = 60.0;
+// MFMAs per tile of one launch: about half a second of one wave
+constexpr uint64_t kLoadMaxLaunchMfmas = 1ull << 24;
+// MFMAs per tile of the calibration launch: about a millisecond
+constexpr uint32_t kLoadCalibrationMfmas = 1u << 15;
+
+struct LoadArgs {
+  LoadSlot* slots;
+  uint32_t visit_base, seed, n_mfmas, chunks;
+  LoadInject inj;
+  LoadRecord* record;
+  float* dump;
+};
+
+template <int DT, bool INJECT, bool DUMP>
+static void launch_load_as(int blocks, uint32_t lds_bytes, const LoadArgs& a) {
+  auto kernel = mfma_load_kernel<DT, INJECT, DUMP>;
+  allow_dynamic_lds(kernel, lds_bytes);
+  hipLaunchKernelGGL(kernel, dim3(blocks), dim3(kLoadThreads), lds_bytes, 0, a.slots,
+                     a.visit_base, a.seed, a.n_mfmas, a.chunks, a.inj, a.record, a.dump);
+}
+
+template <int DT>
+static void launch_load_dt(int blocks, uint32_t lds_bytes, const LoadArgs& a) {
+  if (a.dump) launch_load_as<DT, false, true>(blocks, lds_bytes, a);
+  else if (a.record) launch_load_as<DT, true, false>(blocks, lds_bytes, a);
+  else launch_load_as<DT, false, false>(blocks, lds_bytes, a);
+}
+
+// a.dump selects the dump instantiation, a.record the INJECT one, neither the
+// production kernel
+static void launch_mfma_load(int dtype, int blocks, uint32_t lds_bytes, const LoadArgs& a) {
+  switch (dtype) {
+    case gh::BF16: launch_load_dt<gh::BF16>(blocks, lds_bytes, a); break;
+    case gh::F16: launch_load_dt<gh::F16>(blocks, lds_bytes, a); break;
+    case gh::FP8: launch_load_dt<gh::FP8>(blocks, lds_bytes, a); break;
+    default: launch_load_dt<gh::MXFP4>(blocks, lds_bytes, a); break;
+  }
+  HIP_CHECK(hipGetLastError());
+}
+
+struct LoadResult {
+  int dtype = 0;
+  int cu_total = 0;
+  int launches = 0;
+  int blocks = 0;
+  uint32_t check_every = 0, chunks = 0;
+  double elapsed_ms = 0.0;
+  double floor_tflops = 0.0;
+  std::vector<LoadSlot> slots;
+  bool injected = false, have_record = false;
+  LoadRecord record{};
+};
+
+// seconds == 0: exactly one launch of blocks workgroups (0: 4 x CUs) with
+// chunks chunks of check_every MFMAs per tile. seconds > 0: chunks == 0 lets a
+// short first launch size chunks so that a launch lasts about launch_ms; then
+// launches go back to back, at most two in flight, until the event-timed
+// elapsed time reaches seconds. The slot table is read once at the end.
+static LoadResult run_mfma_load(int dtype, double seconds, int check_every, int64_t chunks_in,
+                                int blocks, double launch_ms, uint32_t seed,
+                                double floor_tflops, const LoadInject* inject) {
+  if (!(seconds >= 0.0) || seconds > kLoadMaxSeconds)
+    throw py::value_error("seconds must be in [0, 60]");
+  if (check_every < 1 || check_every > kLoadMaxCheckEvery || check_every % 2 == 0)
+    throw py::value_error("check_every must be odd and in [1, 4095]");
+  const uint64_t max_chunks = kLoadMaxLaunchMfmas / (uint64_t)check_every;
+  if (chunks_in < 0 || (uint64_t)chunks_in > max_chunks)
+    throw py::value_error("chunks must be in [0, 2^24 / check_every]");
+  if (seconds == 0.0 && chunks_in == 0)
+    throw py::value_error("chunks must be at least 1 when seconds is 0");
+  if (!(launch_ms >= 1.0) || launch_ms > 1000.0)
+    throw py::value_error("launch_ms must be in [1, 1000]");
+  if (!(floor_tflops >= 0.0)) throw py::value_error("floor_tflops must not be negative");
+  if (inject && seconds != 0.0)
+    throw py::value_error("inject_acc needs seconds == 0, the one launch it names");
+
+  LoadResult res;
+  res.dtype = dtype;
+  res.floor_tflops = floor_tflops;
+  res.check_every = (uint32_t)check_every;
+  res.cu_total = current_device_attribute(hipDeviceAttributeMultiprocessorCount);
+  if (blocks == 0) blocks = 4 * res.cu_total;
+  if (blocks < 1 || blocks > kLoadMaxBlocks)
+    throw py::value_error("blocks must be 0 or in [1, 2^14]");
+  res.blocks = blocks;
+  if (inject) {
+    if (inject->visit >= (uint32_t)blocks)
+      throw py::value_error("injected visit is outside the launch");
+    if (inject->chunk >= (uint64_t)chunks_in)
+      throw py::value_error("injected chunk is outside [0, chunks)");
+    if (inject->after >= (uint32_t)check_every)
+      throw py::value_error("injected MFMA is outside [0, check_every)");
+    res.injected = true;
+  }
+  const uint32_t lds_bytes = checked_lds_bytes(0);
+
+  DeviceScope scope;
+  res.slots.assign(gh::kCuSlots, LoadSlot{});
+  const size_t slot_bytes = gh::kCuSlots * sizeof(LoadSlot);
+  LoadSlot* d_slots = (LoadSlot*)scope.alloc(slot_bytes);
+  HIP_CHECK(hipMemset(d_slots, 0, slot_bytes));
+  LoadRecord* d_record = nullptr;
+  if (inject) {
+    d_record = (LoadRecord*)scope.alloc(sizeof(LoadRecord));
+    HIP_CHECK(hipMemset(d_record, 0, sizeof(LoadRecord)));
+  }
+
+  LoadArgs args{d_slots, 0, seed, (uint32_t)check_every, (uint32_t)chunks_in,
+                inject ? *inject : LoadInject{}, d_record, nullptr};
+  auto launch = [&]() {
+    args.visit_base = (uint32_t)((uint64_t)res.launches * blocks);
+    launch_mfma_load(dtype, blocks, lds_bytes, args);
+    ++res.launches;
+  };
+  auto ms_between = [](hipEvent_t a, hipEvent_t b) {
+    float ms = 0.f;
+    HIP_CHECK(hipEventElapsedTime(&ms, a, b));
+    return (double)ms;
+  };
+
+  const double want_ms = seconds * 1e3;
+  hipEvent_t t0 = scope.event(), done[2] = {scope.event(), scope.event()};
+  HIP_CHECK(hipEventRecord(t0, 0));
+  if (seconds == 0.0) {
+    launch();
+    HIP_CHECK(hipEventRecord(done[0], 0));
+    HIP_CHECK(hipEventSynchronize(done[0]));
+    res.elapsed_ms = ms_between(t0, done[0]);
+  } else {
+    if (chunks_in == 0) {
+      // the calibration launch is the run's first: what it checks and issues
+      // counts like any other launch's
+      args.chunks = std::max(1u, kLoadCalibrationMfmas / (uint32_t)check_every);
+      launch();
+      HIP_CHECK(hipEventRecord(done[0], 0));
+      HIP_CHECK(hipEventSynchronize(done[0]));
+      const double cal_ms = std::max(ms_between(t0, done[0]), 1e-3);
+      const double scaled = (double)args.chunks * launch_ms / cal_ms;
+      args.chunks = (uint32_t)std::min((double)max_chunks, std::max(1.0, scaled));
+    }
+    // launch n's end is done[n & 1]; elapsed and last are known up to launch n
+    int first = res.launches;
+    launch();
+    HIP_CHECK(hipEventRecord(done[first & 1], 0));
+    double prev_end = first ? ms_between(t0, done[0]) : 0.0, last = launch_ms;
+    for (int n = first;; ++n) {
+      // launch n is in flight. Another goes behind it unless launch n is
+      // expected to reach the time asked for.
+      const bool more = prev_end + last < want_ms;
+      if (more) {
+        launch();
+        HIP_CHECK(hipEventRecord(done[(n + 1) & 1], 0));
+      }
+      HIP_CHECK(hipEventSynchronize(done[n & 1]));
+      const double end = ms_between(t0, done[n & 1]);
+      last = end - prev_end;
+      prev_end = end;
+      if (more) continue;
+      if (end >= want_ms) break;
+      launch();  // the estimate fell short: one more, alone
+      HIP_CHECK(hipEventRecord(done[(n + 1) & 1], 0));
+    }
+    res.elapsed_ms = prev_end;
+  }
+  res.chunks = args.chunks;
+  HIP_CHECK(hipMemcpy(res.slots.data(), d_slots, slot_bytes, hipMemcpyDeviceToHost));
+  if (inject) {
+    HIP_CHECK(hipMemcpy(&res.record, d_record, sizeof(LoadRecord), hipMemcpyDeviceToHost));
+    res.have_record = res.record.written != 0;
+  }
+  return res;
+}
+
+// test hook: the accumulators of one workgroup's kLoadWaves x kLoadTiles tiles
+// after exactly n_mfmas MFMAs each, through the production packing and loop
+static std::string run_debug_mfma_load_dump(int dtype, int64_t n_mfmas, uint32_t seed,
+                                            uint32_t visit) {
+  if (n_mfmas < 1 || n_mfmas > kLoadMaxCheckEvery)
+    throw py::value_error("mfmas must be in [1, 4095]");
+  const size_t bytes = (size_t)kLoadWaves * kLoadTiles * 256 * sizeof(float);
+  DeviceScope scope;
+  float* d_out = (float*)scope.alloc(bytes);
+  LoadSlot* d_slots = (LoadSlot*)scope.alloc(gh::kCuSlots * sizeof(LoadSlot));
+  HIP_CHECK(hipMemset(d_out, 0xFF, bytes));  // an unwritten element reads as NaN
+  HIP_CHECK(hipMemset(d_slots, 0, gh::kCuSlots * sizeof(LoadSlot)));
+  launch_mfma_load(dtype, 1, checked_lds_bytes(0),
+                   LoadArgs{d_slots, visit, seed, (uint32_t)n_mfmas, 1, LoadInject{}, nullptr,
+                            d_out});
+  HIP_CHECK(hipDeviceSynchronize());
+  std::string host(bytes, '\0');
+  HIP_CHECK(hipMemcpy(&host[0], d_out, bytes, hipMemcpyDeviceToHost));
+  return host;
+}
+
+// ---------------------------------------------------------------------------
 // host API
 // ---------------------------------------------------------------------------
 static py::dict device_info(int device) {
@@ -1668,6 +2144,125 @@ static py::bytes debug_cu_lds_dump(int device, uint64_t lds_bytes, uint32_t seed
   return py::bytes(run_debug_cu_lds_dump(lds_bytes, seed, invert, v));
 }
 
+// -- MFMA load bindings ------------------------------------------------------
+// (visit, wave, tile, chunk, after_mfma, register, mask); what depends on the
+// launch is checked by run_mfma_load
+typedef std::optional<std::tuple<int64_t, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t>>
+    inject_acc_t;
+
+static std::optional<LoadInject> checked_load_inject(const inject_acc_t& in) {
+  if (!in) return std::nullopt;
+  const auto& [visit, wave, tile, chunk, after, reg, mask] = *in;
+  LoadInject inj;
+  inj.visit = checked_index(visit, kLoadMaxBlocks, "injected visit");
+  inj.wave = checked_index(wave, kLoadWaves, "injected wave");
+  inj.tile = checked_index(tile, kLoadTiles, "injected tile");
+  inj.chunk = checked_index(chunk, kLoadMaxLaunchMfmas, "injected chunk");
+  inj.after = checked_index(after, kLoadMaxCheckEvery, "injected MFMA");
+  inj.reg = checked_index(reg, 4, "injected register");
+  inj.mask = checked_mask(mask);
+  return inj;
+}
+
+static double median_of(std::vector<double> v) {
+  if (v.empty()) return 0.0;
+  std::sort(v.begin(), v.end());
+  const size_t n = v.size();
+  return n % 2 ? v[n / 2] : 0.5 * (v[n / 2 - 1] + v[n / 2]);
+}
+
+// clock_mhz and cycles_per_mfma are medians over the covered CUs of each CU's
+// sums over its waves (the table keeps sums, not one entry per wave)
+static py::dict mfma_load_dict(const LoadResult& r) {
+  py::dict d;
+  py::list faulty, locations;
+  std::vector<double> clocks, cycles_per;
+  unsigned long long mfmas = 0, bad_total = 0;
+  int covered = 0;
+  double slowest = 0.0;
+  py::object slowest_cu = py::none();
+  for (uint32_t key = 0; key < gh::kCuSlots; ++key) {
+    const LoadSlot& s = r.slots[key];
+    if (s.visits == 0 && s.simd_seen == 0) continue;
+    ++covered;
+    mfmas += s.mfmas;
+    if (s.ticks != 0) clocks.push_back((double)s.cycles / (double)s.ticks * 100.0);
+    if (s.mfmas != 0) {
+      const double per = (double)s.cycles / (double)s.mfmas;
+      cycles_per.push_back(per);
+      if (per > slowest) {
+        slowest = per;
+        slowest_cu = location_dict(key);
+      }
+    }
+    for (uint32_t simd = 0; simd < gh::kNumSimds; ++simd) {
+      if (s.bad[simd] == 0) continue;
+      bad_total += s.bad[simd];
+      py::dict f = location_dict(key);
+      f["simd"] = simd;
+      f["dtype"] = kDtypeNames[r.dtype];
+      f["bad_elements"] = s.bad[simd];
+      faulty.append(f);
+    }
+    py::dict where = location_dict(key);
+    where["visits"] = s.visits;
+    where["simd_seen"] = s.simd_seen;
+    locations.append(where);
+  }
+  const double flop = (double)mfmas * (double)gh::flop_per_mfma(r.dtype);
+  const double tflops = r.elapsed_ms > 0.0 ? flop / (r.elapsed_ms * 1e-3) / 1e12 : 0.0;
+  if (!slowest_cu.is_none()) slowest_cu["cycles_per_mfma"] = slowest;
+  d["dtype"] = kDtypeNames[r.dtype];
+  d["mfmas"] = mfmas;
+  d["flop"] = mfmas * gh::flop_per_mfma(r.dtype);
+  d["elapsed_ms"] = r.elapsed_ms;
+  d["tflops"] = tflops;
+  d["clock_mhz"] = median_of(clocks);
+  d["cycles_per_mfma"] = median_of(cycles_per);
+  d["launches"] = r.launches;
+  d["blocks"] = r.blocks;
+  d["check_every"] = r.check_every;
+  d["chunks"] = r.chunks;
+  d["tiles_per_wave"] = kLoadTiles;
+  d["cu_total"] = r.cu_total;
+  d["cu_covered"] = covered;
+  d["faulty"] = faulty;
+  d["locations"] = locations;
+  d["slowest_cu"] = slowest_cu;
+  d["floor_tflops"] = r.floor_tflops;
+  d["ok"] = bad_total == 0 && tflops >= r.floor_tflops;
+  if (r.injected) {
+    if (!r.have_record) {
+      d["record"] = py::none();
+    } else {
+      py::dict rec = location_dict(r.record.key);
+      py::list simd;
+      for (int w = 0; w < kLoadWaves; ++w) simd.append(r.record.simd[w]);
+      rec["simd"] = simd;
+      d["record"] = rec;
+    }
+  }
+  return d;
+}
+
+static py::dict mfma_load(int device, const std::string& dtype, double seconds, int check_every,
+                          int64_t chunks, int blocks, double launch_ms, uint32_t seed,
+                          double floor_tflops, inject_acc_t inject_acc) {
+  const int dt = parse_dtype(dtype);
+  const std::optional<LoadInject> inj = checked_load_inject(inject_acc);
+  use_device(device);
+  return mfma_load_dict(run_mfma_load(dt, seconds, check_every, chunks, blocks, launch_ms, seed,
+                                      floor_tflops, inj ? &*inj : nullptr));
+}
+
+static py::bytes debug_mfma_load_dump(int device, const std::string& dtype, int64_t mfmas,
+                                      uint32_t seed, int64_t visit) {
+  const int dt = parse_dtype(dtype);
+  const uint32_t v = checked_index(visit, 1ull << 32, "visit");
+  use_device(device);
+  return py::bytes(run_debug_mfma_load_dump(dt, mfmas, seed, v));
+}
+
 static py::dict burn_in(int device, double hbm_fraction, double hbm_floor_gb_s,
                         bool require_cu_coverage) {
   py::dict result = health_check(device, hbm_floor_gb_s, false);
@@ -1736,6 +2331,18 @@ PYBIND11_MODULE(gpuhealth, m) {
         py::arg("passes") = 1, py::arg("lds_bytes") = 0, py::arg("blocks_per_round") = 0,
         py::arg("max_rounds") = 8, py::arg("inject_lds") = py::none(),
         py::arg("inject_mfma") = py::none(), py::arg("inject_lds_stuck") = py::none());
+  m.attr("MFMA_LOAD_TILES") = kLoadTiles;
+  m.attr("MFMA_LOAD_CHECK_EVERY") = kLoadDefaultCheckEvery;
+  m.def("mfma_load", &mfma_load, py::arg("device") = 0, py::arg("dtype") = "bf16",
+        py::arg("seconds") = 2.0, py::arg("check_every") = kLoadDefaultCheckEvery,
+        py::arg("chunks") = 0, py::arg("blocks") = 0,
+        py::arg("launch_ms") = kLoadDefaultLaunchMs, py::arg("seed") = gh::kDefaultSeed,
+        py::arg("floor_tflops") = 0.0, py::arg("inject_acc") = py::none());
+  m.def("debug_mfma_load_dump", &debug_mfma_load_dump, py::arg("device") = 0,
+        py::arg("dtype") = "bf16", py::arg("mfmas") = 1, py::arg("seed") = gh::kDefaultSeed,
+        py::arg("visit") = 0);
+  m.def("flop_per_mfma", [](const std::string& dtype) {
+    return gh::flop_per_mfma(parse_dtype(dtype)); }, py::arg("dtype"));
   m.def("decode_location", &decode_location_py, py::arg("xcc_id_reg"), py::arg("hw_id_reg"));
   m.def("debug_cu_lds_dump", &debug_cu_lds_dump, py::arg("device") = 0,
         py::arg("lds_bytes") = 0, py::arg("seed") = gh::kDefaultSeed,

@@ -329,4 +329,54 @@ inline void reference_tile(int dtype, uint32_t seed, uint32_t wg, float D[16][16
       D[r][c] = reference_element(dtype, seed, wg, r, c);
 }
 
+// ---------------------------------------------------------------------------
+// MFMA load: a chain of MFMAs on one exact tile that stays exactly checkable
+//
+// Alternating-sign premise: a wave holds A, B and C of an exact tile and issues
+// acc = mfma(A, B, acc), acc = mfma(-A, B, acc), ... starting from acc = C,
+// where -A is A with the sign bit of every element flipped (negate_mask). Every
+// partial sum is C plus a signed subset of the K products of one A·B: for
+// bf16 / f16 / fp8 an integer below 2^13, for MXFP4 a multiple of 1/16 below
+// 2^16. Both fit the fp32 significand, so every accumulation order gives the
+// same bits, as in the premise at the top, and after n MFMAs acc is
+// reference_element (n odd) or C (n even), whatever n is. A chain of any
+// length on hashed data can be compared with == against integer arithmetic.
+//
+// Its one real limit: an error that enters the accumulator is carried to the
+// next check only if it is at least one unit of the data (1 for the integer
+// paths, 1/16 for MXFP4). An error below the ulp of a later partial sum can be
+// rounded away before the check sees it; the check interval (check_every
+// MFMAs) bounds how long that window is.
+// ---------------------------------------------------------------------------
+constexpr uint32_t kLoadWaves = 4;  // waves of one load workgroup, one per SIMD
+constexpr uint32_t kLoadTiles = 4;  // independent exact tiles one wave keeps going
+
+// the per-dword xor that negates every element of a packed A or B operand; MX
+// scales are not touched
+GH_HD inline uint32_t negate_mask(int dtype) {
+  return dtype == MXFP4 ? 0x88888888u : (dtype == FP8 ? 0x80808080u : 0x80008000u);
+}
+
+GH_HD inline uint64_t flop_per_mfma(int dtype) {
+  return 2ull * kTile * kTile * (uint64_t)k_of(dtype);
+}
+
+// Which exact tile (the wg of the generators) tile `tile` of wave `wave` of
+// workgroup visit `visit` works on: different for every wave of every launch.
+// One operand set serves all chunks of a visit: building a set is integer
+// hashing (the expectation is computed off the matrix pipe) and was measured at
+// about 40 us a wave, 330 us for MXFP4, against 7 to 9 us for a chunk of 239
+// MFMAs per tile (docs/benchmarks.md, "MFMA load"). It is paid once per launch
+// and not once per check.
+GH_HD inline uint32_t load_tile_index(uint32_t visit, uint32_t wave, uint32_t tile) {
+  return (visit * kLoadWaves + wave) * kLoadTiles + tile;
+}
+
+// acc[row][col] of tile wg after n_mfmas MFMAs of the alternating chain
+GH_HD inline float expected_after(int dtype, uint32_t seed, uint32_t wg, uint32_t row,
+                                  uint32_t col, uint64_t n_mfmas) {
+  return (n_mfmas & 1u) ? reference_element(dtype, seed, wg, row, col)
+                        : (float)gen_c(seed, wg, dtype, row, col);
+}
+
 }  // namespace gh

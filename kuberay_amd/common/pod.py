@@ -25,6 +25,8 @@ these MI355X-native differences:
 from __future__ import annotations
 
 import json
+import logging
+import math
 import os
 from typing import Dict, List, Optional
 
@@ -47,6 +49,10 @@ from ..models.raycluster import RayCluster, RayNodeType, WorkerGroupSpec
 from ..utils import constants as C
 from ..utils import names
 from ..utils.resources import container_gpu_count, find_container_port
+
+logger = logging.getLogger("kuberay.pod")
+# values of amd.com/gpu-burn-in-load-seconds that were already warned about
+_bad_load_values_seen: set = set()
 
 SHARED_MEMORY_MOUNT_PATH = "/dev/shm"
 RAY_LOG_VOLUME_NAME = "ray-logs"
@@ -342,22 +348,54 @@ def init_liveness_and_readiness_probe(
         ray_container.readiness_probe = probe
 
 
-def init_gpu_burn_in_startup_probe(ray_container: Container) -> None:
+def gpu_burn_in_load_seconds(annotations: Optional[Dict[str, str]]) -> Optional[float]:
+    """The value of ``amd.com/gpu-burn-in-load-seconds``: a number in (0, 60],
+    or None when the annotation is absent or is no such number (logged)."""
+    raw = (annotations or {}).get(C.GPU_BURN_IN_LOAD_SECONDS_ANNOTATION_KEY)
+    if raw is None:
+        return None
+    try:
+        seconds = float(raw)
+    except (TypeError, ValueError):
+        seconds = float("nan")
+    if not 0.0 < seconds <= C.GPU_BURN_IN_LOAD_MAX_SECONDS:  # false for a NaN too
+        # every reconcile builds the pod again: a warning the first time a
+        # value is seen, debug after that
+        first = raw not in _bad_load_values_seen
+        if first and len(_bad_load_values_seen) < 1024:
+            _bad_load_values_seen.add(raw)
+        logger.log(logging.WARNING if first else logging.DEBUG,
+                   "ignoring %s=%r: not a number of seconds in (0, %g]",
+                   C.GPU_BURN_IN_LOAD_SECONDS_ANNOTATION_KEY, raw,
+                   C.GPU_BURN_IN_LOAD_MAX_SECONDS)
+        return None
+    return seconds
+
+
+def init_gpu_burn_in_startup_probe(ray_container: Container,
+                                   load_seconds: Optional[float] = None) -> None:
     """MI355X burn-in as a startupProbe (opt-in, annotation
     ``amd.com/gpu-burn-in: "true"`` on a GPU worker template): the HBM
     pattern sweep and the exact MFMA checks of
     ``python -m kuberay_amd.gpu.probe --deep`` must pass once before the
     kubelet starts the liveness and readiness probes, which stay as built.
+    ``load_seconds`` (annotation ``amd.com/gpu-burn-in-load-seconds``) adds
+    the MFMA load and its time to the probe's timeout.
     A user-supplied startupProbe is kept."""
     if ray_container.startup_probe is not None:
         return
+    command = C.GPU_BURN_IN_PROBE_COMMAND
+    timeout = C.GPU_BURN_IN_PROBE_TIMEOUT_SECONDS
+    if load_seconds is not None:
+        command += f" --load-seconds {load_seconds:g}"
+        timeout += math.ceil(load_seconds) + C.GPU_BURN_IN_LOAD_PROBE_OVERHEAD_SECONDS
     probe = Probe(
-        timeout_seconds=C.GPU_BURN_IN_PROBE_TIMEOUT_SECONDS,
+        timeout_seconds=timeout,
         period_seconds=C.GPU_BURN_IN_PROBE_PERIOD_SECONDS,
         success_threshold=1,
         failure_threshold=C.GPU_BURN_IN_PROBE_FAILURE_THRESHOLD,
     )
-    probe.exec_ = ExecAction(command=["bash", "-c", C.GPU_BURN_IN_PROBE_COMMAND])
+    probe.exec_ = ExecAction(command=["bash", "-c", command])
     ray_container.startup_probe = probe
 
 
@@ -786,7 +824,8 @@ def build_pod(
         burn_in = (template.metadata.annotations or {}).get(
             C.GPU_BURN_IN_ANNOTATION_KEY, "").lower() == "true"
         if gpu_probe and burn_in:
-            init_gpu_burn_in_startup_probe(ray_container)
+            init_gpu_burn_in_startup_probe(
+                ray_container, gpu_burn_in_load_seconds(template.metadata.annotations))
     return pod
 
 

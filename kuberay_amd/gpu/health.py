@@ -57,6 +57,12 @@ class HealthReport:
     cu_total: Optional[int] = None
     cu_covered: Optional[int] = None
     cu_faulty: Optional[List[str]] = None
+    # MFMA load of the burn-in level; None unless it was asked for
+    mfma_load_ok: Optional[bool] = None
+    mfma_load_tflops: Optional[Dict[str, float]] = None
+    mfma_load_clock_mhz: Optional[Dict[str, float]] = None
+    mfma_load_faulty: Optional[List[str]] = None
+    mfma_load_ok_by_dtype: Optional[Dict[str, bool]] = None
 
 
 def _rocm_smi_ok() -> bool:
@@ -134,21 +140,75 @@ def _cu_problem(where) -> str:
     return f"cu {_cu_name(where)}: " + "; ".join(parts)
 
 
+MFMA_LOAD_DTYPES = ("bf16", "f16", "fp8", "mxfp4")
+MAX_MFMA_LOAD_SECONDS = 60.0
+# TFLOP/s floors of the MFMA load: half of the lowest 2 s run per data type on
+# an MI355X, three runs on each of two nodes (2313 / 2330 / 2361 / 6783,
+# docs/benchmarks.md "MFMA load"), rounded down to two digits. Half leaves room for the spread between
+# devices, a busy neighbour and a power-capped clock; the collapse the floor is
+# for (a parked engine clock) is several-fold.
+DEFAULT_MFMA_FLOOR_TFLOPS = {"bf16": 1100.0, "f16": 1100.0, "fp8": 1100.0,
+                             "mxfp4": 3300.0}
+
+
+def _mfma_load(native, device: int, load_seconds: float, floors: Dict[str, float]):
+    """The MFMA load, ``load_seconds / 4`` per data type. Returns (ok by data
+    type, tflops, clock_mhz, faulty, problems)."""
+    if not hasattr(native, "mfma_load"):
+        return {}, {}, {}, [], ["mfma load: asked for, but this native module "
+                                "has no mfma_load"]
+    ok, tflops, clock, faulty, problems = {}, {}, {}, [], []
+    for dtype in MFMA_LOAD_DTYPES:
+        floor = float(floors[dtype])
+        before = len(problems)
+        r = native.mfma_load(device, dtype, seconds=load_seconds / len(MFMA_LOAD_DTYPES),
+                             floor_tflops=floor)
+        tflops[dtype], clock[dtype] = float(r["tflops"]), float(r["clock_mhz"])
+        for f in r["faulty"]:
+            faulty.append(f"{dtype} {_cu_name(f, short=True)} simd {f['simd']}")
+            problems.append(f"mfma load {dtype}: cu {_cu_name(f)} simd {f['simd']}: "
+                            f"{f['bad_elements']} bad elements")
+        if tflops[dtype] < floor:
+            problems.append(
+                f"mfma load {dtype}: {tflops[dtype]:.0f} TFLOP/s below the floor of "
+                f"{floor:.0f} (clock {clock[dtype]:.0f} MHz, "
+                f"{float(r['cycles_per_mfma']):.1f} cycles/MFMA)")
+        elif not r["ok"] and not r["faulty"]:
+            problems.append(f"mfma load {dtype}: not ok")
+        ok[dtype] = len(problems) == before
+    return ok, tflops, clock, faulty, problems
+
+
 def check_gpu_burn_in(device: int = 0,
                       hbm_fraction: float = DEFAULT_BURN_IN_HBM_FRACTION,
                       hbm_floor_gb_s: float = DEFAULT_HBM_FLOOR_GB_S,
-                      require_cu_coverage: bool = False) -> HealthReport:
+                      require_cu_coverage: bool = False,
+                      load_seconds: float = 0.0,
+                      mfma_floor_tflops: Optional[Dict[str, float]] = None) -> HealthReport:
     """Burn-in level: the full gate of ``check_gpu_health``, then the exact
     MFMA verification on the bf16, f16, fp8 and MXFP4 data paths, then a
     data-verifying pattern sweep over ``hbm_fraction`` of the free HBM, then
     the CU sweep (LDS march on every CU, the exact MFMA tiles on every SIMD).
     A faulty CU is unhealthy and named in ``detail``; CUs the sweep did not
     reach are reported, and unhealthy only with ``require_cu_coverage``.
+    With ``load_seconds > 0`` the MFMA load follows: every matrix pipe kept
+    busy on self-checking data for a quarter of that time per data type. A
+    wrong element, or a rate under ``mfma_floor_tflops`` (by data type, over
+    ``DEFAULT_MFMA_FLOOR_TFLOPS``), is unhealthy and named in ``detail``.
     Raises GpuHealthError on non-GPU hosts; ``detail`` names what failed."""
     if not gpu_node():
         raise GpuHealthError("not a GPU node (/dev/kfd missing)")
     if not 0.0 < hbm_fraction <= 1.0:
         raise ValueError(f"hbm_fraction must be in (0, 1], got {hbm_fraction}")
+    if not 0.0 <= load_seconds <= MAX_MFMA_LOAD_SECONDS:
+        raise ValueError(f"load_seconds must be in [0, {MAX_MFMA_LOAD_SECONDS:.0f}], "
+                         f"got {load_seconds}")
+    floors = dict(DEFAULT_MFMA_FLOOR_TFLOPS)
+    for dtype, floor in (mfma_floor_tflops or {}).items():
+        if dtype not in floors or not float(floor) >= 0.0:
+            raise ValueError(f"mfma_floor_tflops: {dtype}={floor} is not a data type of "
+                             f"{MFMA_LOAD_DTYPES} with a floor of at least 0")
+        floors[dtype] = float(floor)
 
     rocm_ok = _rocm_smi_ok()
     native = _load_native()
@@ -187,6 +247,16 @@ def check_gpu_burn_in(device: int = 0,
             problems.append(f"cu coverage {cu_covered}/{cu_total} after "
                             f"{sweep['rounds']} rounds")
             healthy = healthy and not require_cu_coverage
+    load_ok = load_by_dtype = load_tflops = load_clock = load_faulty = None
+    if load_seconds > 0.0:
+        try:
+            load_by_dtype, load_tflops, load_clock, load_faulty, load_problems = _mfma_load(
+                native, device, load_seconds, floors)
+        except RuntimeError as e:
+            return _hip_failure(e, rocm_ok)
+        problems.extend(load_problems)
+        load_ok = not load_problems
+        healthy = healthy and load_ok
     if not rocm_ok:
         problems.append("rocm-smi did not respond")
     return HealthReport(
@@ -200,6 +270,9 @@ def check_gpu_burn_in(device: int = 0,
         hbm_pattern_ok=bool(result["hbm_pattern_ok"]),
         hbm_bytes_checked=int(pattern["bytes_checked"]),
         hbm_flipped_bits=int(pattern["flipped_bits"]),
+        mfma_load_ok=load_ok, mfma_load_tflops=load_tflops,
+        mfma_load_clock_mhz=load_clock, mfma_load_faulty=load_faulty,
+        mfma_load_ok_by_dtype=load_by_dtype,
     )
 
 

@@ -8,6 +8,12 @@ instead (HBM pattern sweep + exact MFMA checks + the per-CU sweep of LDS and
 SIMDs; with the flag, a CU the sweep could not reach fails it); the pod
 builder injects it as a startupProbe on GPU workers whose template carries
 ``amd.com/gpu-burn-in: "true"``.
+
+``--deep --load-seconds S [--mfma-floor-tflops DTYPE=N ...]`` adds the MFMA
+load to the burn-in level: S seconds of self-checking MFMA on every matrix
+pipe, a quarter per data type, with a TFLOP/s floor (annotation
+``amd.com/gpu-burn-in-load-seconds``). Its fields appear in the output only
+when it ran.
 """
 from __future__ import annotations
 
@@ -15,8 +21,9 @@ import argparse
 import json
 import sys
 
-from .health import (DEFAULT_BURN_IN_HBM_FRACTION, GpuHealthError,
-                     check_gpu_burn_in, check_gpu_health)
+from .health import (DEFAULT_BURN_IN_HBM_FRACTION, MAX_MFMA_LOAD_SECONDS,
+                     MFMA_LOAD_DTYPES, GpuHealthError, check_gpu_burn_in,
+                     check_gpu_health)
 
 
 def main(argv=None) -> int:
@@ -35,14 +42,43 @@ def main(argv=None) -> int:
     parser.add_argument("--require-cu-coverage", action="store_true",
                         help="with --deep: unhealthy unless the CU sweep "
                              "reached every CU of the device")
+    parser.add_argument("--load-seconds", type=float, default=0.0,
+                        help="with --deep: seconds of self-checking MFMA load, "
+                             "a quarter per data type (0: none, at most 60)")
+    parser.add_argument("--mfma-floor-tflops", action="append", default=[],
+                        metavar="DTYPE=N",
+                        help="with --load-seconds: TFLOP/s floor of one data "
+                             "type (bf16, f16, fp8, mxfp4); may be repeated")
     args = parser.parse_args(argv)
+    if args.load_seconds and not args.deep:
+        parser.error("--load-seconds needs --deep")
+    if args.mfma_floor_tflops and not args.load_seconds:
+        parser.error("--mfma-floor-tflops needs --load-seconds")
+    load = {}
+    if args.load_seconds:
+        # the load's own arguments are refused here, as usage errors; the
+        # plain --deep path is as it was
+        if not 0.0 < args.load_seconds <= MAX_MFMA_LOAD_SECONDS:
+            parser.error(f"--load-seconds must be in (0, {MAX_MFMA_LOAD_SECONDS:.0f}]")
+        floors = {}
+        for item in args.mfma_floor_tflops:
+            dtype, sep, value = item.partition("=")
+            try:
+                floors[dtype] = float(value)
+            except ValueError:
+                sep = ""
+            if not sep or dtype not in MFMA_LOAD_DTYPES or not floors[dtype] >= 0.0:
+                parser.error(f"--mfma-floor-tflops wants DTYPE=N with DTYPE one of "
+                             f"{', '.join(MFMA_LOAD_DTYPES)} and N >= 0, got {item!r}")
+        load = {"load_seconds": args.load_seconds, "mfma_floor_tflops": floors or None}
 
     try:
         if args.deep:
             report = check_gpu_burn_in(device=args.device,
                                        hbm_fraction=args.hbm_fraction,
                                        hbm_floor_gb_s=args.hbm_floor_gb_s,
-                                       require_cu_coverage=args.require_cu_coverage)
+                                       require_cu_coverage=args.require_cu_coverage,
+                                       **load)
         else:
             report = check_gpu_health(device=args.device, quick=args.quick,
                                       hbm_floor_gb_s=args.hbm_floor_gb_s)
@@ -52,6 +88,8 @@ def main(argv=None) -> int:
     if args.deep:
         # the CU sweep's fields appear when the native module ran one
         swept = report.cu_total is not None
+        # and the MFMA load's when it was asked for
+        loaded = report.mfma_load_ok is not None
         if args.json_out:
             out = {
                 "healthy": report.healthy, "mfma_ok": report.mfma_ok,
@@ -63,10 +101,20 @@ def main(argv=None) -> int:
             if swept:
                 out.update(cu_total=report.cu_total, cu_covered=report.cu_covered,
                            cu_faulty=report.cu_faulty)
+            if loaded:
+                out.update(mfma_load_ok=report.mfma_load_ok,
+                           mfma_load_tflops=report.mfma_load_tflops,
+                           mfma_load_clock_mhz=report.mfma_load_clock_mhz,
+                           mfma_load_faulty=report.mfma_load_faulty)
             print(json.dumps(out))
         else:
             cu = (f" cu_total={report.cu_total} cu_covered={report.cu_covered} "
                   f"cu_faulty={report.cu_faulty}") if swept else ""
+            if loaded:
+                cu += (f" mfma_load_ok={report.mfma_load_ok} "
+                       f"mfma_load_tflops={report.mfma_load_tflops} "
+                       f"mfma_load_clock_mhz={report.mfma_load_clock_mhz} "
+                       f"mfma_load_faulty={report.mfma_load_faulty}")
             print(f"healthy={report.healthy} mfma_ok={report.mfma_ok} "
                   f"hbm_gb_s={report.hbm_gb_s} rocm_smi_ok={report.rocm_smi_ok} "
                   f"mfma_exact={report.mfma_exact} "

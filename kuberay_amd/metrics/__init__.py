@@ -115,6 +115,14 @@ class OperatorMetrics:
             "1 when the named check of the node's last GPU burn-in passed "
             "(hbm_pattern, mfma_bf16, mfma_f16, mfma_fp8, mfma_mxfp4)",
             ["node", "check"], registry=r)
+        self.gpu_mfma_load_tflops = Gauge(
+            "kuberay_mi355x_gpu_mfma_load_tflops",
+            "TFLOP/s the node's GPU sustained in the last burn-in MFMA load",
+            ["node", "dtype"], registry=r)
+        self.gpu_mfma_load_clock_mhz = Gauge(
+            "kuberay_mi355x_gpu_mfma_load_clock_mhz",
+            "Engine clock the waves of the last burn-in MFMA load measured "
+            "(median over compute units)", ["node", "dtype"], registry=r)
 
     # -- hooks used by the reconcilers ----------------------------------
     def observe_cluster_ready(self, cluster) -> None:
@@ -171,6 +179,13 @@ class OperatorMetrics:
         for dtype in ("bf16", "f16", "fp8", "mxfp4"):
             ok = (report.mfma_exact or {}).get(dtype, False)
             self.gpu_burn_in_ok.labels(node, f"mfma_{dtype}").set(1 if ok else 0)
+        # the MFMA load's, only when the report has them
+        for dtype, tflops in (getattr(report, "mfma_load_tflops", None) or {}).items():
+            self.gpu_mfma_load_tflops.labels(node, dtype).set(tflops)
+        for dtype, mhz in (getattr(report, "mfma_load_clock_mhz", None) or {}).items():
+            self.gpu_mfma_load_clock_mhz.labels(node, dtype).set(mhz)
+        for dtype, ok in (getattr(report, "mfma_load_ok_by_dtype", None) or {}).items():
+            self.gpu_burn_in_ok.labels(node, f"mfma_load_{dtype}").set(1 if ok else 0)
 
     def exposition(self) -> bytes:
         return generate_latest(self.registry)

@@ -229,6 +229,23 @@ GPU_BURN_IN_PROBE_PERIOD_SECONDS = 10
 # A failed burn-in is a finding, not a flake: two attempts, then the
 # container is restarted.
 GPU_BURN_IN_PROBE_FAILURE_THRESHOLD = 2
+# Pod-template annotation: a number of seconds in (0, 60] on a template that
+# also carries amd.com/gpu-burn-in: "true" adds the MFMA load to the burn-in
+# (``--load-seconds <n>``) and raises the startup probe's timeout by that time
+# plus the overhead below. Without the burn-in annotation it does nothing; a
+# value that is no such number is logged and ignored.
+GPU_BURN_IN_LOAD_SECONDS_ANNOTATION_KEY = "amd.com/gpu-burn-in-load-seconds"
+GPU_BURN_IN_LOAD_MAX_SECONDS = 60.0
+# What ``--load-seconds S`` adds to the wall time of the probe beyond S itself:
+# three times the largest excess measured on an MI355X over S in {1, 4, 8},
+# three runs each, interleaved with plain runs, rounded up to whole seconds.
+# The plain probe took 2.3 s to 8.5 s in that session, the less the longer the
+# device had been left alone since the probe before it, so the excess has no
+# single value; this is the least favourable one, against the fastest plain run
+# (9.80 s - 1 s - 2.30 s = 6.50 s -> 19.5 s). Against a plain run in the same
+# position, right after another probe (8.5 s), it is 0.3 s at the most.
+# Measurement: docs/benchmarks.md, "MFMA load".
+GPU_BURN_IN_LOAD_PROBE_OVERHEAD_SECONDS = 20
 
 # Device nodes every ROCm container needs (AMD k8s device plugin mounts these
 # automatically when amd.com/gpu is requested; we also support explicit
