@@ -12,6 +12,11 @@ store change pays.
 
     python benchmark/perf-tests/store_profile.py --clusters 200 --steps 3
 
+``--micro`` instead times one stored object three ways, for the bench's
+worker pod, head pod and RayCluster: the engine's decode from the stored
+sections, blob assembly + ``json.loads``, and ``engine.copy_tree`` of the
+parsed tree (the cost of creating the containers alone, the decoder's floor).
+
 ``--root DIR`` profiles another checkout of this repository (for a
 before/after on the same host); every site is looked up by name and skipped
 where a checkout does not have it. CPU-only: no GPU is touched.
@@ -121,6 +126,19 @@ def instrument(sites: Sites) -> None:
             if fn is not None:
                 setattr(backend_cls, name,
                         sites.wrap(f"NativeBackend.{name}", fn))
+        # the reads themselves, inside the engine: trees decoded from the
+        # sections, or blobs assembled for json.loads (the row above)
+        store_cls = getattr(native_mod.engine, "NativeStore", None)
+        for site, names in (
+                ("native decode of stored objects (NativeStore.*_tree[s])",
+                 ("fetch_tree", "remove_tree", "list_trees",
+                  "history_since_trees")),
+                ("blob assembly for json.loads (NativeStore reads)",
+                 ("fetch", "remove", "list_blobs", "history_since"))):
+            for name in names:
+                fn = getattr(store_cls, name, None)
+                if fn is not None:
+                    setattr(store_cls, name, sites.wrap(site, fn))
     json.dumps = dumps
     server_cls._notify = sites.wrap("InMemoryApiServer._notify", notify_flagged)
 
@@ -141,6 +159,17 @@ def instrument_reconciler(sites: Sites) -> None:
     objects_mod.K8sModel.clone = sites.wrap(
         "K8sModel.clone", objects_mod.K8sModel.clone)
 
+    objects_mod.K8sModel.to_dict = sites.wrap(
+        "K8sModel.to_dict", objects_mod.K8sModel.to_dict)
+    objects_mod.K8sModel.from_dict = classmethod(sites.wrap(
+        "K8sModel.from_dict", objects_mod.K8sModel.from_dict.__func__))
+    create_wire = getattr(client_mod.InMemoryClient, "create_wire", None)
+    if create_wire is not None:
+        client_mod.InMemoryClient.create_wire = sites.wrap(
+            "client.create_wire (pods as wire dicts)", create_wire)
+    client_mod.InMemoryClient.create = sites.wrap(
+        "client.create (typed)", client_mod.InMemoryClient.create)
+
     real_get = client_mod.InMemoryClient.get
     clock = time.thread_time
 
@@ -160,6 +189,57 @@ def instrument_reconciler(sites: Sites) -> None:
             setattr(cls, name, sites.wrap(f"RayClusterReconciler.{name}", fn))
 
 
+def micro() -> int:
+    """One bench cluster brought to Ready, then per object: decode from the
+    sections, blob + json.loads and copy_tree, best of five timed loops."""
+    from kuberay_amd._native import engine
+    from kuberay_amd.testing import ControlPlane, simple_raycluster
+
+    cp = ControlPlane(kubelet_delay=0.0, workers=2, record_events=False,
+                      requeue_seconds=3600, poll_seconds=1.0,
+                      kubelet_executors=2)
+    cp.start()
+    try:
+        name = "bench-r0-s0-0000"
+        cp.client.create(simple_raycluster(name, workers=3, gpus_per_worker=1))
+        if not cp.wait_cluster_state("default", name, "ready", timeout=60):
+            raise RuntimeError("cluster never became ready")
+        store = cp.server._backend._store
+        pods = [p["metadata"]["name"] for p in cp.server.list("Pod")]
+        subjects = [
+            ("worker pod", "Pod", next(n for n in pods if "worker" in n)),
+            ("head pod", "Pod", next(n for n in pods if "head" in n)),
+            ("RayCluster", "RayCluster", name)]
+
+        def best_us(fn, loops=5000):
+            best = float("inf")
+            for _ in range(5):
+                t0 = time.perf_counter()
+                for _ in range(loops):
+                    fn()
+                best = min(best, (time.perf_counter() - t0) / loops)
+            return best * 1e6
+
+        print("| object | bytes | native decode us | blob + json.loads us | "
+              "ratio | copy_tree us |")
+        print("|---|---|---|---|---|---|")
+        for label, kind, obj_name in subjects:
+            key = (kind, "default", obj_name)
+            blob = store.fetch(*key)
+            tree = json.loads(blob)
+            decoded = store.fetch_tree(*key)
+            if type(decoded) is not dict or decoded != tree:
+                raise RuntimeError(f"{label}: decoder fell back or differs")
+            t_dec = best_us(lambda: store.fetch_tree(*key))
+            t_loads = best_us(lambda: json.loads(store.fetch(*key)))
+            t_copy = best_us(lambda: engine.copy_tree(tree))
+            print(f"| {label} | {len(blob)} | {t_dec:.1f} | {t_loads:.1f} | "
+                  f"{t_loads / t_dec:.2f}x | {t_copy:.1f} |")
+    finally:
+        cp.stop()
+    return 0
+
+
 def main() -> int:
     parser = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     parser.add_argument("--clusters", type=int, default=200)
@@ -171,11 +251,16 @@ def main() -> int:
                         help="checkout to profile (default: this one)")
     parser.add_argument("--json", action="store_true",
                         help="print the table as one JSON line as well")
+    parser.add_argument("--micro", action="store_true",
+                        help="time decode / json.loads / copy_tree of the "
+                             "bench objects instead of profiling steps")
     args = parser.parse_args()
 
     root = os.path.abspath(args.root or os.path.join(
         os.path.dirname(os.path.abspath(__file__)), "..", ".."))
     sys.path.insert(0, root)
+    if args.micro:
+        return micro()
     import bench  # the checkout's own step definition
     from kuberay_amd.testing import ControlPlane
 

@@ -5,8 +5,9 @@ Extensions:
   * gpuhealth  — HIP/gfx950 on-device health probes and burn-in
                  (gpuhealth.hip over gpuhealth_ref.hpp)
   * engine     — C++ control-plane core: object cache + indices + native
-                 JSON encoding and model-tree copies (engine.cpp
-                 bindings over store_core.hpp and tree_copy.hpp)
+                 JSON encoding and decoding and model-tree copies (engine.cpp
+                 bindings over store_core.hpp, json_decode.hpp and
+                 tree_copy.hpp)
 
 Build: ``python -m kuberay_amd._native.build`` or ``__graft_entry__.build()``.
 """
@@ -60,7 +61,8 @@ def build_engine(force: bool = False) -> Path:
     if not src.exists():
         return out
     if not force and not _needs_rebuild(src, out, HERE / "store_core.hpp",
-                                        HERE / "tree_copy.hpp"):
+                                        HERE / "tree_copy.hpp",
+                                        HERE / "json_decode.hpp"):
         return out
     cxx = os.environ.get("CXX", "g++")
     cmd = [

@@ -31,6 +31,8 @@
 #include <unordered_set>
 #include <vector>
 
+#define KUBERAY_JSON_WITH_PYTHON
+#include "json_decode.hpp"
 #include "store_core.hpp"
 #include "tree_copy.hpp"
 
@@ -542,6 +544,79 @@ class NativeStore {
     return to_bytes(*b);
   }
 
+  // -- tree-returning reads (json_decode.hpp) ---------------------------
+  // Each hands the reader the object as json.loads of the assembled blob
+  // would give it, built straight from the sections. An object the decoder
+  // does not reproduce comes back as that blob (bytes) instead, for the
+  // caller to json.loads: per object, so a remove never has to be repeated
+  // and one odd object does not send a whole list down the slow path. Either
+  // way the object counts once in blobs_assembled. The store mutex is
+  // released before the first Python object is built.
+  py::object decode(const Blob& b) {
+    {
+      kuberay_json::TreeBuilder builder;
+      kuberay_json::Tokenizer<kuberay_json::TreeBuilder> tok(builder);
+      const kuberay_json::Result r =
+          tok.entry(b.rest.get(), b.meta.get(), b.status.get(), b.whole);
+      if (r == kuberay_json::Result::kOk) {
+        core_.note_decode(true);
+        return py::reinterpret_steal<py::object>(builder.release());
+      }
+    }
+    if (PyErr_Occurred()) PyErr_Clear();  // json.loads meets it again
+    core_.note_decode(false);
+    return to_bytes(b);
+  }
+
+  py::object fetch_tree(const std::string& kind, const std::string& ns,
+                        const std::string& name) {
+    std::optional<Blob> b = core_.fetch(kind, ns, name);
+    if (!b) return py::none();
+    core_.note_assembled(1, b->size());
+    return decode(*b);
+  }
+
+  py::object remove_tree(const std::string& kind, const std::string& ns,
+                         const std::string& name,
+                         std::optional<int64_t> event_rv) {
+    std::optional<Blob> b = core_.remove(kind, ns, name, event_rv);
+    if (!b) return py::none();
+    core_.note_assembled(1, b->size());
+    return decode(*b);
+  }
+
+  py::list list_trees(const std::string& kind,
+                      const std::optional<std::string>& ns,
+                      const LabelList& selector) {
+    std::vector<Blob> blobs = core_.list(kind, ns, selector);
+    py::list out;
+    size_t bytes = 0;
+    for (const Blob& b : blobs) {
+      bytes += b.size();
+      out.append(decode(b));
+    }
+    core_.note_assembled(blobs.size(), bytes);
+    return out;
+  }
+
+  // [(event type, tree or bytes, rv override or None)], as history_since.
+  py::object history_since_trees(
+      int64_t rv, const std::optional<std::unordered_set<std::string>>& kinds) {
+    std::optional<std::vector<HistoryItem>> items =
+        core_.history_since(rv, kinds ? &*kinds : nullptr);
+    if (!items) return py::none();
+    py::list out;
+    size_t bytes = 0;
+    for (const HistoryItem& h : *items) {
+      bytes += h.blob.size();
+      py::object override_rv = py::none();
+      if (h.rv_override) override_rv = py::int_(*h.rv_override);
+      out.append(py::make_tuple(h.event_type, decode(h.blob), override_rv));
+    }
+    core_.note_assembled(items->size(), bytes);
+    return out;
+  }
+
   std::optional<std::string> rv(const std::string& kind, const std::string& ns,
                                 const std::string& name) const {
     return core_.rv(kind, ns, name);
@@ -666,6 +741,8 @@ class NativeStore {
     d["bytes_assembled"] = s.bytes_assembled;
     d["fallbacks"] = s.fallbacks;
     d["history_appends"] = s.history_appends;
+    d["trees_decoded"] = s.trees_decoded;
+    d["decode_fallbacks"] = s.decode_fallbacks;
     return d;
   }
 
@@ -728,6 +805,13 @@ PYBIND11_MODULE(engine, m) {
            py::arg("has_finalizers") = false, py::arg("deletion_ts") = "",
            py::arg("service_view") = std::nullopt)
       .def("fetch", &NativeStore::fetch)
+      .def("fetch_tree", &NativeStore::fetch_tree)
+      .def("remove_tree", &NativeStore::remove_tree, py::arg("kind"),
+           py::arg("ns"), py::arg("name"), py::arg("event_rv") = std::nullopt)
+      .def("list_trees", &NativeStore::list_trees, py::arg("kind"),
+           py::arg("ns") = std::nullopt, py::arg("selector") = LabelList())
+      .def("history_since_trees", &NativeStore::history_since_trees,
+           py::arg("rv"), py::arg("kinds") = std::nullopt)
       .def("rv", &NativeStore::rv)
       .def("peek", &NativeStore::peek)
       .def("contains", &NativeStore::contains)

@@ -142,6 +142,7 @@ struct Stats {
   uint64_t full_encodes = 0, partial_encodes = 0, bytes_encoded = 0;
   uint64_t blobs_assembled = 0, bytes_assembled = 0;
   uint64_t fallbacks = 0, history_appends = 0;
+  uint64_t trees_decoded = 0, decode_fallbacks = 0;
 };
 
 inline std::string make_key(const std::string& kind, const std::string& ns,
@@ -405,6 +406,12 @@ class StoreCore {
     bytes_assembled_.fetch_add(bytes, std::memory_order_relaxed);
   }
   void note_fallback() { fallbacks_.fetch_add(1, std::memory_order_relaxed); }
+  // A read handed out as a tree built from the sections / as bytes for
+  // json.loads because the decoder does not reproduce the object.
+  void note_decode(bool decoded) {
+    (decoded ? trees_decoded_ : decode_fallbacks_)
+        .fetch_add(1, std::memory_order_relaxed);
+  }
 
   Stats stats() const {
     Stats s;
@@ -415,6 +422,8 @@ class StoreCore {
     s.bytes_assembled = bytes_assembled_.load(std::memory_order_relaxed);
     s.fallbacks = fallbacks_.load(std::memory_order_relaxed);
     s.history_appends = history_appends_.load(std::memory_order_relaxed);
+    s.trees_decoded = trees_decoded_.load(std::memory_order_relaxed);
+    s.decode_fallbacks = decode_fallbacks_.load(std::memory_order_relaxed);
     return s;
   }
 
@@ -552,6 +561,7 @@ class StoreCore {
   std::atomic<uint64_t> full_encodes_{0}, partial_encodes_{0}, bytes_encoded_{0};
   std::atomic<uint64_t> blobs_assembled_{0}, bytes_assembled_{0};
   std::atomic<uint64_t> fallbacks_{0}, history_appends_{0};
+  std::atomic<uint64_t> trees_decoded_{0}, decode_fallbacks_{0};
 };
 
 }  // namespace kuberay_store

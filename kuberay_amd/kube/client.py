@@ -184,6 +184,14 @@ class InMemoryClient(KubeClient):
         out = self.server.create(data, assume_owned=True)
         return type(obj).from_dict(out)
 
+    def create_wire(self, data):
+        """Create from an already-dumped, kind-tagged wire dict (what
+        ``create`` makes of a model). The store takes the dict over and
+        stamps it; it is returned as stored, and no typed response is built.
+        Callers find this method by ``getattr``: clients without it (REST)
+        are given models through ``create``."""
+        return self.server.create(data, assume_owned=True)
+
     def get(self, model, namespace, name):
         out = self.server.get(_kind_of(model), namespace, name)
         return model.from_dict(out)
@@ -199,10 +207,15 @@ class InMemoryClient(KubeClient):
         obj.metadata.generation = out["metadata"].get("generation")
         return type(obj).from_dict(out)
 
-    def update_status(self, obj):
+    def update_status(self, obj, *, discard_result=False):
+        """With ``discard_result`` the passed object's resourceVersion is
+        refreshed as always, and None is returned instead of a model of the
+        response, for callers that would throw that model away."""
         out = self.server.update(obj.to_dict(), subresource="status",
                                  assume_owned=True)
         obj.metadata.resource_version = out["metadata"]["resourceVersion"]
+        if discard_result:
+            return None
         return type(obj).from_dict(out)
 
     def patch(self, model, namespace, name, patch, subresource=None):

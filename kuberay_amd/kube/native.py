@@ -4,9 +4,11 @@
 The engine owns the encoding: a write hands it the dict tree and it encodes,
 indexes, computes the pod view and records the watch-history entry in one
 call; a status write re-encodes metadata + status only. Objects live in the
-C++ heap as shared JSON sections; reads parse on demand; the reconcile hot
-loop reads precomputed pod and Service views without touching any JSON at
-all.
+C++ heap as shared JSON sections; a read has the engine build the dict tree
+straight from those sections (json_decode.hpp), and gets the assembled blob
+back as bytes, to json.loads here, for an object the decoder does not
+reproduce; the reconcile hot loop reads precomputed pod and Service views
+without touching any JSON at all.
 
 Trees the native encoder declines (tuples, subclasses, non-str keys, big
 ints, NaN/Inf, lone surrogates, very deep nesting) take the json.dumps +
@@ -58,6 +60,11 @@ class NativeBackend:
     # of each part can be told apart. Results are the same either way.
     native_encode = os.environ.get("KUBERAY_STORE_NATIVE_ENCODE", "1") != "0"
     status_splice = os.environ.get("KUBERAY_STORE_STATUS_SPLICE", "1") != "0"
+    # Reads: with it on, the engine builds the dict tree straight from the
+    # stored sections (json_decode.hpp); off, it assembles a blob for
+    # json.loads as before. An object the decoder does not reproduce comes
+    # back as that blob (bytes) either way and is parsed here.
+    native_decode = os.environ.get("KUBERAY_STORE_NATIVE_DECODE", "1") != "0"
 
     def __init__(self, history_limit: int = 1024) -> None:
         self._store = engine.NativeStore(history_limit)
@@ -111,6 +118,9 @@ class NativeBackend:
             self.put(key, obj, event_type)
 
     def fetch(self, key: Key) -> Optional[Dict[str, Any]]:
+        if self.native_decode:
+            obj = self._store.fetch_tree(*key)
+            return _loads(obj) if type(obj) is bytes else obj
         blob = self._store.fetch(*key)
         return _loads(blob) if blob is not None else None
 
@@ -129,7 +139,10 @@ class NativeBackend:
                event_rv: Optional[int] = None) -> Optional[Dict[str, Any]]:
         """Remove and return the object; with ``event_rv`` the DELETED
         history entry (carrying that rv) is recorded in the same call."""
-        blob = self._store.remove(key[0], key[1], key[2], event_rv)
+        if self.native_decode:
+            blob = self._store.remove_tree(key[0], key[1], key[2], event_rv)
+        else:
+            blob = self._store.remove(key[0], key[1], key[2], event_rv)
         if blob is None:
             return None
         n = self._kind_counts.get(key[0], 0) - 1
@@ -137,10 +150,17 @@ class NativeBackend:
             self._kind_counts[key[0]] = n
         else:
             self._kind_counts.pop(key[0], None)
-        return _loads(blob)
+        return _loads(blob) if type(blob) is bytes else blob
 
     def list(self, kind: str, namespace: Optional[str],
              selector: Optional[Dict[str, str]]) -> List[Dict[str, Any]]:
+        if self.native_decode:
+            objs = self._store.list_trees(kind, namespace,
+                                          list((selector or {}).items()))
+            for i, obj in enumerate(objs):
+                if type(obj) is bytes:
+                    objs[i] = _loads(obj)
+            return objs
         blobs = self._store.list_blobs(kind, namespace,
                                        list((selector or {}).items()))
         return [_loads(b) for b in blobs]
@@ -184,12 +204,16 @@ class NativeBackend:
     def history_since(self, rv: int, kinds: Optional[set] = None):
         """[(event type, object)] with resourceVersion > rv, oldest first,
         decoded on demand; None when rv predates the retained window."""
-        rows = self._store.history_since(rv, kinds)
+        if self.native_decode:
+            rows = self._store.history_since_trees(rv, kinds)
+        else:
+            rows = self._store.history_since(rv, kinds)
         if rows is None:
             return None
         out = []
-        for etype, blob, rv_override in rows:
-            obj = _loads(blob)
+        for etype, obj, rv_override in rows:
+            if type(obj) is bytes:
+                obj = _loads(obj)
             if rv_override is not None:
                 # a delete is its own revision; the sections still carry
                 # the object's last one

@@ -22,9 +22,10 @@ from typing import Dict, List, Optional
 
 from ..common import association, gcs_ft, ingress as ingresslib, pod as podlib, rbac, service as servicelib
 from ..kube import objects as k8s
-from ..kube.client import KubeClient
+from ..kube.client import InMemoryClient, KubeClient
 from ..kube.controller import Reconciler, Request, Result
 from ..kube.events import EventRecorder, NullRecorder
+from ..kube.objects import deep_copy
 from ..kube.store import AlreadyExistsError, NotFoundError, now_iso
 from ..models.raycluster import (
     ClusterState,
@@ -169,6 +170,7 @@ class RayClusterReconciler(Reconciler):
     # it replaced. Results are the same either way.
     group_pod_reuse = os.environ.get("KUBERAY_GROUP_POD_REUSE", "1") != "0"
     service_views = os.environ.get("KUBERAY_SERVICE_VIEW", "1") != "0"
+    pod_wire_create = os.environ.get("KUBERAY_POD_WIRE_CREATE", "1") != "0"
 
     def __init__(self, client: KubeClient, recorder: Optional[EventRecorder] = None,
                  expectations=None, batch_scheduler=None,
@@ -187,6 +189,20 @@ class RayClusterReconciler(Reconciler):
         # computing it costs ~150 µs — per-pod recomputation was ~15% of a
         # 2000-pod bench step.
         self._spec_hash_cache: Dict[str, tuple] = {}
+        # status writes whose response nobody reads skip building its model
+        # where the client can (InMemoryClient.update_status)
+        self._status_kwargs = (
+            {"discard_result": True}
+            if getattr(type(client), "update_status", None)
+            is InMemoryClient.update_status else {})
+
+    def _wire_create(self):
+        """The client's create-from-wire-dict method when pods go that way:
+        the switch is on, the client has one, and no batch scheduler needs
+        the pod as a model (add_metadata_to_pod)."""
+        if not self.pod_wire_create or self.batch_scheduler is not None:
+            return None
+        return getattr(self.client, "create_wire", None)
 
     def _spec_hash(self, cluster) -> str:
         """Memoized hash_without_replicas_and_workers_to_delete[:63].
@@ -723,22 +739,52 @@ class RayClusterReconciler(Reconciler):
         if self.batch_scheduler is not None:
             self.batch_scheduler.add_metadata_to_pod(self.client, cluster,
                                                      "headgroup", pod)
-        created = self.client.create(pod)
+        create_wire = self._wire_create()
+        if create_wire is not None:
+            # dumped once and handed over; the stored dict carries the name
+            data = pod.to_dict()
+            data["kind"] = pod.kind
+            created_name = create_wire(data)["metadata"]["name"]
+        else:
+            created_name = self.client.create(pod).metadata.name
         self.expectations.expect_create_pod(namespace, cluster.metadata.name,
-                                            "__head__", created.metadata.name)
+                                            "__head__", created_name)
         self.recorder.eventf(cluster, "Normal", "CreatedHeadPod",
-                             "Created head Pod %s", created.metadata.name)
+                             "Created head Pod %s", created_name)
 
     def _create_worker_pod(self, cluster: RayCluster, group: WorkerGroupSpec,
                            replica_index: int = 0, host_index: int = 0,
                            replica_grp_name: Optional[str] = None,
-                           prototype: Optional[k8s.Pod] = None,
-                           keep_prototype: bool = False) -> Optional[k8s.Pod]:
+                           prototype=None, keep_prototype: bool = False):
         """Create one worker pod: built from the group spec, or, given the
         ``prototype`` an earlier call of the same scale-up returned, a copy
         of it with this replica's index. With ``keep_prototype`` the pod is
-        returned as built, before a batch scheduler edits it."""
+        returned as built, before a batch scheduler edits it.
+
+        Where pods are created from wire dicts (_wire_create) the prototype
+        is the first pod's dumped dict, copied before the store stamps it,
+        and a further replica is a copy of that dict with its index label:
+        no model is cloned, dumped or validated for it."""
         namespace = cluster.metadata.namespace or "default"
+        create_wire = self._wire_create()
+        if create_wire is not None and (prototype is None
+                                        or isinstance(prototype, dict)):
+            if prototype is None:
+                pod = self._build_worker_pod(cluster, group, replica_index,
+                                             host_index, replica_grp_name)
+                data = pod.to_dict()
+                data["kind"] = pod.kind
+            else:
+                data = deep_copy(prototype)
+                data["metadata"]["labels"][C.RAY_WORKER_REPLICA_INDEX_KEY] = \
+                    str(replica_index)
+            kept = deep_copy(data) if keep_prototype else None
+            created_name = create_wire(data)["metadata"]["name"]
+            self.expectations.expect_create_pod(
+                namespace, cluster.metadata.name, group.group_name, created_name)
+            self.recorder.eventf(cluster, "Normal", "CreatedWorkerPod",
+                                 "Created worker Pod %s", created_name)
+            return kept
         if prototype is None:
             pod = self._build_worker_pod(cluster, group, replica_index,
                                          host_index, replica_grp_name)
@@ -900,7 +946,7 @@ class RayClusterReconciler(Reconciler):
         # single status write per reconcile, only on change
         if {k: v for k, v in new_status.items() if k != "lastUpdateTime"} != \
            {k: v for k, v in old_status.items() if k != "lastUpdateTime"}:
-            self.client.update_status(cluster)
+            self.client.update_status(cluster, **self._status_kwargs)
 
     def _update_endpoints(self, cluster: RayCluster) -> None:
         svc_name = names.head_service_name(C.KIND_RAYCLUSTER, cluster.spec,
@@ -945,6 +991,6 @@ class RayClusterReconciler(Reconciler):
 
     def _update_status_if_changed(self, cluster: RayCluster) -> None:
         try:
-            self.client.update_status(cluster)
+            self.client.update_status(cluster, **self._status_kwargs)
         except NotFoundError:
             pass
