@@ -124,7 +124,10 @@
 //                    an xor into one accumulator register of lane 0 after a
 //                    named MFMA of a named chunk (its own instantiation), and
 //                    debug_mfma_load_dump (the accumulators of one workgroup
-//                    after exactly n MFMAs, through the production loop).
+//                    after exactly n MFMAs, through the production loop; with
+//                    alternate=False its instantiation alone keeps +A where
+//                    -A belongs, so the same loop leaves C + n·A·B and every
+//                    count of issued MFMAs gives another answer).
 //
 // What must agree between host and device (pattern, generators, encoders,
 // reference) is in gpuhealth_ref.hpp.
@@ -1455,12 +1458,15 @@ __device__ inline void xor_accumulator(frag_cd_t (&acc)[kLoadTiles], uint32_t ti
 // n_mfmas per tile and chunk: the production host passes an odd number, so a
 // chunk ends on C + A·B; the dump hook passes any. dump (DUMP only) receives
 // the accumulators as the last chunk left them, tile (wave, t) row-major at
-// dump + 256 * (kLoadTiles * wave + t).
+// dump + 256 * (kLoadTiles * wave + t). dump_same_sign (read by DUMP only; it
+// lies in what was padding behind inj, so no other argument moves) puts A where
+// -A belongs: the same loop then leaves C + n_mfmas·A·B, which tells every
+// count from every other where the alternating chain tells odd from even.
 template <int DT, bool INJECT = false, bool DUMP = false>
 __global__ __launch_bounds__(kLoadThreads) void mfma_load_kernel(
     LoadSlot* __restrict__ slots, uint32_t visit_base, uint32_t seed, uint32_t n_mfmas,
-    uint32_t chunks, LoadInject inj, LoadRecord* __restrict__ record,
-    float* __restrict__ dump) {
+    uint32_t chunks, LoadInject inj, uint32_t dump_same_sign,
+    LoadRecord* __restrict__ record, float* __restrict__ dump) {
   const int lane = threadIdx.x & 63;
   const uint32_t wave = threadIdx.x >> 6;
   const uint32_t visit = visit_base + blockIdx.x;
@@ -1480,6 +1486,9 @@ __global__ __launch_bounds__(kLoadThreads) void mfma_load_kernel(
     const uint32_t wg = gh::load_tile_index(visit, wave, (uint32_t)t);
     pos[t] = pack_exact_operands<DT>(seed, wg, lane);
     neg[t] = negated_a<DT>(pos[t]);
+    if constexpr (DUMP) {
+      if (dump_same_sign) neg[t] = pos[t];
+    }
     for (uint32_t r = 0; r < 4; ++r) {
       c0[t][r] = gh::expected_after(DT, seed, wg, row0 + r, col, 0);
       want[t][r] = gh::expected_after(DT, seed, wg, row0 + r, col, n_mfmas);
@@ -1595,6 +1604,7 @@ struct LoadArgs {
   LoadInject inj;
   LoadRecord* record;
   float* dump;
+  uint32_t dump_same_sign = 0;  // the dump hook's alternate=False
 };
 
 template <int DT, bool INJECT, bool DUMP>
@@ -1602,7 +1612,8 @@ static void launch_load_as(int blocks, uint32_t lds_bytes, const LoadArgs& a) {
   auto kernel = mfma_load_kernel<DT, INJECT, DUMP>;
   allow_dynamic_lds(kernel, lds_bytes);
   hipLaunchKernelGGL(kernel, dim3(blocks), dim3(kLoadThreads), lds_bytes, 0, a.slots,
-                     a.visit_base, a.seed, a.n_mfmas, a.chunks, a.inj, a.record, a.dump);
+                     a.visit_base, a.seed, a.n_mfmas, a.chunks, a.inj, a.dump_same_sign,
+                     a.record, a.dump);
 }
 
 template <int DT>
@@ -1758,9 +1769,10 @@ static LoadResult run_mfma_load(int dtype, double seconds, int check_every, int6
 }
 
 // test hook: the accumulators of one workgroup's kLoadWaves x kLoadTiles tiles
-// after exactly n_mfmas MFMAs each, through the production packing and loop
+// after exactly n_mfmas MFMAs each, through the production packing and loop;
+// alternate == false issues +A every time (C + n_mfmas·A·B)
 static std::string run_debug_mfma_load_dump(int dtype, int64_t n_mfmas, uint32_t seed,
-                                            uint32_t visit) {
+                                            uint32_t visit, bool alternate) {
   if (n_mfmas < 1 || n_mfmas > kLoadMaxCheckEvery)
     throw py::value_error("mfmas must be in [1, 4095]");
   const size_t bytes = (size_t)kLoadWaves * kLoadTiles * 256 * sizeof(float);
@@ -1771,7 +1783,7 @@ static std::string run_debug_mfma_load_dump(int dtype, int64_t n_mfmas, uint32_t
   HIP_CHECK(hipMemset(d_slots, 0, gh::kCuSlots * sizeof(LoadSlot)));
   launch_mfma_load(dtype, 1, checked_lds_bytes(0),
                    LoadArgs{d_slots, visit, seed, (uint32_t)n_mfmas, 1, LoadInject{}, nullptr,
-                            d_out});
+                            d_out, alternate ? 0u : 1u});
   HIP_CHECK(hipDeviceSynchronize());
   std::string host(bytes, '\0');
   HIP_CHECK(hipMemcpy(&host[0], d_out, bytes, hipMemcpyDeviceToHost));
@@ -2256,11 +2268,11 @@ static py::dict mfma_load(int device, const std::string& dtype, double seconds, 
 }
 
 static py::bytes debug_mfma_load_dump(int device, const std::string& dtype, int64_t mfmas,
-                                      uint32_t seed, int64_t visit) {
+                                      uint32_t seed, int64_t visit, bool alternate) {
   const int dt = parse_dtype(dtype);
   const uint32_t v = checked_index(visit, 1ull << 32, "visit");
   use_device(device);
-  return py::bytes(run_debug_mfma_load_dump(dt, mfmas, seed, v));
+  return py::bytes(run_debug_mfma_load_dump(dt, mfmas, seed, v, alternate));
 }
 
 static py::dict burn_in(int device, double hbm_fraction, double hbm_floor_gb_s,
@@ -2333,6 +2345,7 @@ PYBIND11_MODULE(gpuhealth, m) {
         py::arg("inject_mfma") = py::none(), py::arg("inject_lds_stuck") = py::none());
   m.attr("MFMA_LOAD_TILES") = kLoadTiles;
   m.attr("MFMA_LOAD_CHECK_EVERY") = kLoadDefaultCheckEvery;
+  m.attr("MFMA_LOAD_CALIBRATION_MFMAS") = kLoadCalibrationMfmas;
   m.def("mfma_load", &mfma_load, py::arg("device") = 0, py::arg("dtype") = "bf16",
         py::arg("seconds") = 2.0, py::arg("check_every") = kLoadDefaultCheckEvery,
         py::arg("chunks") = 0, py::arg("blocks") = 0,
@@ -2340,7 +2353,7 @@ PYBIND11_MODULE(gpuhealth, m) {
         py::arg("floor_tflops") = 0.0, py::arg("inject_acc") = py::none());
   m.def("debug_mfma_load_dump", &debug_mfma_load_dump, py::arg("device") = 0,
         py::arg("dtype") = "bf16", py::arg("mfmas") = 1, py::arg("seed") = gh::kDefaultSeed,
-        py::arg("visit") = 0);
+        py::arg("visit") = 0, py::kw_only(), py::arg("alternate") = true);
   m.def("flop_per_mfma", [](const std::string& dtype) {
     return gh::flop_per_mfma(parse_dtype(dtype)); }, py::arg("dtype"));
   m.def("decode_location", &decode_location_py, py::arg("xcc_id_reg"), py::arg("hw_id_reg"));

@@ -14,7 +14,7 @@ import pytest
 
 from gpuhealth_model import DTYPES
 from mfma_load_model import (TILES, WAVES, accumulator_after_mfma, expected_dump,
-                             flop_per_mfma, tile_index)
+                             flop_per_mfma, nonzero_target, tile_index)
 
 pytestmark = pytest.mark.gpu
 
@@ -118,18 +118,6 @@ def test_clean_run(native, clean, dtype):
 # ---------------------------------------------------------------------------
 # 3. a seeded accumulator fault
 # ---------------------------------------------------------------------------
-def _nonzero_target(dtype, seed, visit, after):
-    """(wave, tile, register) of lane 0 whose accumulator is not zero right
-    after MFMA ``after``: lane 0 holds D[r][0] in register r."""
-    for wave in range(WAVES):
-        for tile in range(TILES):
-            acc = accumulator_after_mfma(dtype, seed, tile_index(visit, wave, tile), after)
-            for reg in range(4):
-                if acc[reg, 0] != 0:
-                    return wave, tile, reg
-    raise AssertionError("every candidate accumulator is zero")
-
-
 @pytest.mark.parametrize("dtype", DTYPES)
 def test_seeded_fault_is_found_once_and_where_it_ran(native, clean, dtype):
     """The sign bit of a non-zero accumulator in the middle of chunk 1 of 4:
@@ -137,7 +125,7 @@ def test_seeded_fault_is_found_once_and_where_it_ran(native, clean, dtype):
     end of that chunk. One bad element and no more: the reset to C at the chunk
     boundary keeps chunks 2 and 3 clean."""
     visit, chunk, after = 5, 1, CHECK_EVERY // 2
-    wave, tile, reg = _nonzero_target(dtype, native.DEFAULT_SEED, visit, after)
+    wave, tile, reg = nonzero_target(dtype, native.DEFAULT_SEED, visit, after)
     r = _small(native, dtype, inject_acc=(visit, wave, tile, chunk, after, reg, 0x80000000))
     rec = r["record"]
     print(f"{dtype}: inject wave {wave} tile {tile} reg {reg}; record {rec}; faulty {r['faulty']}")
