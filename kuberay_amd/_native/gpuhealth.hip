@@ -128,9 +128,52 @@
 //                    alternate=False its instantiation alone keeps +A where
 //                    -A belongs, so the same loop leaves C + n·A·B and every
 //                    count of issued MFMAs gives another answer).
+//   * gemm_exact   — opt-in (milliseconds, single-shot): every check above
+//                    builds its MFMA operands in registers. This one takes
+//                    them the way a real gfx950 GEMM or attention kernel does:
+//                    D = A·B + C on bf16 / f16 matrices in device memory, a
+//                    64 x 64 tile per workgroup of four waves, staged global ->
+//                    LDS without a VGPR (global_load_lds_dwordx4) into two
+//                    swizzled LDS stages behind workgroup barriers, A read
+//                    with ds_read_b128 and the row-major B with the
+//                    transposed ds_read_b64_tr_b16, through
+//                    mfma_f32_16x16x32, fp32 D by plain stores. The data are
+//                    integers in [-8, 8] hashed from the full row and column
+//                    (gen_gemm_int), |D| < 2^24 for K <= 65536 (the host
+//                    refuses a larger K, M or N above 65536, and anything
+//                    that is no multiple of 64, with ValueError), so D is
+//                    compared with == against integer dot products that one
+//                    thread per element recomputes from the generators, off
+//                    the matrix pipe. A bad tile is named by the XCC/SE/SH/CU
+//                    its workgroup ran on. Measured lane map of the transposed
+//                    read (debug_lds_tr_dump, tests/test_gpu_gemm_exact.py):
+//                    within each group of 16 lanes, lane l handing in four
+//                    consecutive 16-bit words in[l][0..3] receives
+//                    out[l][e] = in[4 e + l / 4][l % 4]: the 4 x 16 block
+//                    that lanes 4 e .. 4 e + 3 point at row by row comes back
+//                    transposed, column l to lane l (gpuhealth_gemm.hip has the details).
+//                    Default shape: K = 1024 and the smallest square M = N, a
+//                    multiple of 64, that gives every CU two workgroups
+//                    (1472 on 256 CUs). elapsed_ms and tflops of the one cold
+//                    launch are reported for information; there is no floor.
+//                    Cannot show: A and B of this size are served largely from
+//                    L2 / MALL after the fill's first touch, so HBM proper
+//                    stays the pattern sweep's job; the low mantissa bits of
+//                    the operands are still never set; fp8 and MXFP4 are not
+//                    staged through LDS (they need the ..._tr_b8 / ..._tr_b4
+//                    reads and scale staging); nothing here is sustained, one
+//                    launch of microseconds at whatever clock the device is
+//                    at; a CU the dispatcher gave no workgroup is not covered
+//                    (cu_seen says how many were). Test hooks:
+//                    gemm_exact(inject=), an xor into one 16-bit element of A
+//                    or B in device memory between the fill and the GEMM;
+//                    debug_gemm_dump (the raw A, B, C and D of the same code
+//                    path); debug_lds_tr_dump; gemm_operand.
 //
 // What must agree between host and device (pattern, generators, encoders,
-// reference) is in gpuhealth_ref.hpp.
+// reference) is in gpuhealth_ref.hpp. The kernels of gemm_exact ("Burn-in,
+// part 5") and their host code are in gpuhealth_gemm.hip, a translation unit of
+// its own (the reason is at its top); this file binds them.
 //
 // Build: hipcc --offload-arch=gfx950 (see kuberay_amd/_native/build.py).
 // Wavefront width is 64 on CDNA4 — all wave math below hard-codes 64.
@@ -149,6 +192,7 @@
 #include <utility>
 #include <vector>
 
+#include "gpuhealth_gemm.hpp"
 #include "gpuhealth_ref.hpp"
 
 namespace py = pybind11;
@@ -2275,6 +2319,98 @@ static py::bytes debug_mfma_load_dump(int device, const std::string& dtype, int6
   return py::bytes(run_debug_mfma_load_dump(dt, mfmas, seed, v, alternate));
 }
 
+// -- GEMM check bindings (Burn-in, part 5: gpuhealth_gemm.hip) ---------------
+// (operand "a" or "b", row, col, 16-bit xor mask)
+typedef std::optional<std::tuple<std::string, int64_t, int64_t, int64_t>> inject_gemm_t;
+
+static std::optional<ghgemm::Inject> checked_gemm_inject(const inject_gemm_t& in) {
+  if (!in) return std::nullopt;
+  const auto& [operand, row, col, mask] = *in;
+  if (operand != "a" && operand != "b")
+    throw py::value_error("injected operand must be a or b (got '" + operand + "')");
+  if (mask <= 0 || mask > 0xFFFF) throw py::value_error("xor mask must be a non-zero 16-bit value");
+  ghgemm::Inject inj;
+  inj.is_a = operand == "a";
+  inj.row = checked_index(row, 1ull << 32, "injected row");
+  inj.col = checked_index(col, 1ull << 32, "injected column");
+  inj.mask = (uint32_t)mask;
+  return inj;
+}
+
+static py::dict gemm_exact_dict(const ghgemm::Result& r) {
+  py::dict d;
+  py::list faulty;
+  for (const ghgemm::FaultyTile& f : r.faulty) {
+    py::dict t = location_dict(f.key);
+    t["tile"] = py::make_tuple(f.tile_row, f.tile_col);
+    t["mismatches"] = f.stats.mismatches;
+    t["first_bad"] = py::make_tuple(f.stats.first_bad / r.n, f.stats.first_bad % r.n);
+    faulty.append(t);
+  }
+  const double flop = 2.0 * (double)r.m * (double)r.n * (double)r.k;
+  d["dtype"] = kDtypeNames[r.dtype];
+  d["m"] = r.m;
+  d["n"] = r.n;
+  d["k"] = r.k;
+  d["ok"] = r.mismatches == 0;
+  d["mismatches"] = r.mismatches;
+  if (r.first_bad >= 0)
+    d["first_bad"] = py::make_tuple(r.first_bad / r.n, r.first_bad % r.n, r.got, r.expected);
+  else
+    d["first_bad"] = py::none();
+  d["faulty"] = faulty;
+  d["workgroups"] = r.workgroups;
+  d["cu_total"] = r.cu_total;
+  d["cu_seen"] = r.cu_seen;
+  d["elapsed_ms"] = r.elapsed_ms;
+  // for information: one cold launch, nothing is gated on it
+  d["tflops"] = r.elapsed_ms > 0.0 ? flop / (r.elapsed_ms * 1e-3) / 1e12 : 0.0;
+  return d;
+}
+
+static py::dict gemm_exact(int device, const std::string& dtype, int64_t m, int64_t n, int64_t k,
+                           uint32_t seed, inject_gemm_t inject) {
+  const int dt = parse_dtype(dtype);
+  const std::optional<ghgemm::Inject> inj = checked_gemm_inject(inject);
+  use_device(device);
+  return gemm_exact_dict(ghgemm::run_gemm_exact(dt, m, n, k, seed, inj ? &*inj : nullptr));
+}
+
+// test hook: the raw A, B, C and D of the same fill, inject and GEMM
+static py::dict debug_gemm_dump(int device, const std::string& dtype, int64_t m, int64_t n,
+                                int64_t k, uint32_t seed, inject_gemm_t inject) {
+  const int dt = parse_dtype(dtype);
+  const std::optional<ghgemm::Inject> inj = checked_gemm_inject(inject);
+  if (m > 4096 || n > 4096 || k > 4096)
+    throw py::value_error("the dump takes m, n and k of at most 4096");
+  use_device(device);
+  ghgemm::Dump dump;
+  (void)ghgemm::run_gemm_exact(dt, m, n, k, seed, inj ? &*inj : nullptr, &dump);
+  py::dict d;
+  d["a"] = py::bytes(dump.a);
+  d["b"] = py::bytes(dump.b);
+  d["c"] = py::bytes(dump.c);
+  d["d"] = py::bytes(dump.d);
+  return d;
+}
+
+static std::vector<std::vector<int>> debug_lds_tr_dump(int device) {
+  use_device(device);
+  return ghgemm::run_debug_lds_tr_dump();
+}
+
+static int gemm_operand(const std::string& dtype, const std::string& which, int64_t row,
+                        int64_t col, uint32_t seed) {
+  const int dt = parse_dtype(dtype);
+  if (dt != gh::BF16 && dt != gh::F16)
+    throw py::value_error("the GEMM check runs bf16 and f16 only");
+  if (which != "a" && which != "b" && which != "c")
+    throw py::value_error("which must be a, b or c (got '" + which + "')");
+  return gh::gen_gemm_int(seed, dt, which == "a" ? gh::GEN_A : which == "b" ? gh::GEN_B : gh::GEN_C,
+                          checked_index(row, 1ull << 32, "row"),
+                          checked_index(col, 1ull << 32, "column"));
+}
+
 static py::dict burn_in(int device, double hbm_fraction, double hbm_floor_gb_s,
                         bool require_cu_coverage) {
   py::dict result = health_check(device, hbm_floor_gb_s, false);
@@ -2354,6 +2490,17 @@ PYBIND11_MODULE(gpuhealth, m) {
   m.def("debug_mfma_load_dump", &debug_mfma_load_dump, py::arg("device") = 0,
         py::arg("dtype") = "bf16", py::arg("mfmas") = 1, py::arg("seed") = gh::kDefaultSeed,
         py::arg("visit") = 0, py::kw_only(), py::arg("alternate") = true);
+  m.attr("GEMM_DEFAULT_K") = ghgemm::kDefaultK;
+  m.attr("GEMM_WORKGROUPS_PER_CU") = ghgemm::kWorkgroupsPerCu;
+  m.def("gemm_exact", &gemm_exact, py::arg("device") = 0, py::arg("dtype") = "bf16",
+        py::arg("m") = 0, py::arg("n") = 0, py::arg("k") = 0,
+        py::arg("seed") = gh::kDefaultSeed, py::arg("inject") = py::none());
+  m.def("debug_gemm_dump", &debug_gemm_dump, py::arg("device") = 0, py::arg("dtype") = "bf16",
+        py::arg("m") = 64, py::arg("n") = 64, py::arg("k") = 64,
+        py::arg("seed") = gh::kDefaultSeed, py::arg("inject") = py::none());
+  m.def("debug_lds_tr_dump", &debug_lds_tr_dump, py::arg("device") = 0);
+  m.def("gemm_operand", &gemm_operand, py::arg("dtype"), py::arg("which"), py::arg("row"),
+        py::arg("col"), py::arg("seed") = gh::kDefaultSeed);
   m.def("flop_per_mfma", [](const std::string& dtype) {
     return gh::flop_per_mfma(parse_dtype(dtype)); }, py::arg("dtype"));
   m.def("decode_location", &decode_location_py, py::arg("xcc_id_reg"), py::arg("hw_id_reg"));

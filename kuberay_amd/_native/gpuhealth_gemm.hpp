@@ -1,0 +1,65 @@
+// gpuhealth_gemm — what gpuhealth.hip (bindings) and gpuhealth_gemm.hip
+// (kernels and their host code) share of the burn-in's GEMM check: plain
+// structs and two functions, no HIP and no pybind11 types. The two files are
+// separate translation units so that the GEMM kernels can be compiled with a
+// switch of their own (kuberay_amd/_native/build.py) while every older kernel
+// is compiled exactly as before.
+#pragma once
+
+#include <cstdint>
+#include <string>
+#include <vector>
+
+namespace ghgemm {
+
+constexpr uint32_t kDefaultK = 1024;
+// the default M = N is the smallest multiple of 64 whose tiles give every CU
+// at least this many workgroups
+constexpr uint32_t kWorkgroupsPerCu = 2;
+
+struct TileStats {
+  unsigned long long mismatches;
+  unsigned long long first_bad;  // row * N + col, ~0 when clean
+};
+
+// Test hook: an xor into one 16-bit element of A or B in device memory,
+// between the fill and the GEMM.
+struct Inject {
+  bool is_a = true;
+  uint32_t row = 0, col = 0, mask = 0;
+};
+
+struct FaultyTile {
+  uint32_t tile_row, tile_col, key;  // key: gh::location_key of where it ran
+  TileStats stats;
+};
+
+struct Result {
+  int dtype = 0;
+  uint32_t m = 0, n = 0, k = 0;
+  uint64_t mismatches = 0;
+  int64_t first_bad = -1;  // row * N + col
+  float got = 0.f, expected = 0.f;
+  std::vector<FaultyTile> faulty;
+  int workgroups = 0, cu_total = 0, cu_seen = 0;  // cu_seen: distinct places in where[]
+  double elapsed_ms = 0.0;
+};
+
+struct Dump {
+  std::string a, b, c, d;
+};
+
+// On the current device. m, n, k of 0 take the default: k = kDefaultK, m = n =
+// the smallest multiple of 64 that gives every CU kWorkgroupsPerCu workgroups.
+// Throws std::invalid_argument for m, n or k that is no positive multiple of
+// 64, k above gh::kGemmMaxK (exactness) or m, n above gh::kGemmMaxMN (a bound
+// on what one call allocates), a data type other than bf16 / f16 and an
+// injected element outside its matrix; std::runtime_error for a failing HIP
+// call. Single-shot: one fill, one GEMM launch (timed with events), one check.
+Result run_gemm_exact(int dtype, int64_t m, int64_t n, int64_t k, uint32_t seed,
+                      const Inject* inject = nullptr, Dump* dump = nullptr);
+
+// one wave's transposed LDS read of words that hold their own index: 64 x 4
+std::vector<std::vector<int>> run_debug_lds_tr_dump();
+
+}  // namespace ghgemm

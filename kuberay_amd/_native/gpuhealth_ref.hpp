@@ -3,8 +3,9 @@
 // Everything that has to agree bit-for-bit between the host and the gfx950
 // kernels in gpuhealth.hip lives here as plain functions that compile for both
 // sides (GH_HD): the HBM sweep pattern, the operand generators of the exact
-// MFMA check, the encoders to bf16 / f16 / OCP e4m3 / e2m1 bit patterns, and
-// the exact reference product. No HIP, no pybind11 — tests/native/
+// MFMA check, the encoders to bf16 / f16 / OCP e4m3 / e2m1 bit patterns, the
+// exact reference product, and the matrix generator and reference of the GEMM
+// check. No HIP, no pybind11 — tests/native/
 // gpuhealth_ref_check.cpp drives it as a stand-alone g++ program.
 //
 // Exactness premise: bf16 / f16 / fp8 operands are integers in [-8, 8], so a
@@ -377,6 +378,54 @@ GH_HD inline float expected_after(int dtype, uint32_t seed, uint32_t wg, uint32_
                                   uint32_t col, uint64_t n_mfmas) {
   return (n_mfmas & 1u) ? reference_element(dtype, seed, wg, row, col)
                         : (float)gen_c(seed, wg, dtype, row, col);
+}
+
+// ---------------------------------------------------------------------------
+// GEMM check: D = A·B + C on whole matrices in device memory
+//
+// elem_hash packs i << 8 ^ k and so cannot index a matrix; this generator
+// hashes the full 32-bit row and column, the row first and the column into its
+// result, so (r, c) and (c, r) are unrelated. Exactness premise: A (M x K) and
+// B (K x N) hold integers in [-8, 8] as bf16 or f16 and C integers in [-8, 8]
+// as fp32, so every partial sum is an integer and |D| <= 64 K + 8 < 2^24 for
+// K <= kGemmMaxK = 65536. Every accumulation order, whatever the tiling and
+// the split of K, gives the same fp32 value, and == is the compare. The cost is
+// that of the premise at the top: the low mantissa bits of every operand are 0.
+// ---------------------------------------------------------------------------
+constexpr uint32_t kGemmTile = 64;     // a workgroup's tile of D, and the K step of a stage
+constexpr uint32_t kGemmMaxK = 65536;  // 64 K + 8 < 2^24
+constexpr uint32_t kGemmMaxMN = 65536;  // not needed for exactness: bounds what one call allocates
+
+// the per-matrix part of the hash; which is GEN_A, GEN_B or GEN_C
+GH_HD inline uint32_t gemm_matrix_hash(uint32_t seed, int dtype, uint32_t which) {
+  return mix32(seed ^ (((uint32_t)dtype * 8u + which + 1u) * 0x9E3779B9u));
+}
+GH_HD inline int gemm_int_of(uint32_t matrix_hash, uint32_t row, uint32_t col) {
+  return (int)((mix32(mix32(matrix_hash ^ row) + col) >> 8) % 17u) - 8;
+}
+// A[row][col] (row of M, col of K), B[row][col] (row of K, col of N) or
+// C[row][col]: an integer in [-8, 8]
+GH_HD inline int gen_gemm_int(uint32_t seed, int dtype, uint32_t which, uint32_t row,
+                              uint32_t col) {
+  return gemm_int_of(gemm_matrix_hash(seed, dtype, which), row, col);
+}
+
+// D[row][col] of the K-deep product, in integer arithmetic only
+GH_HD inline int32_t gemm_reference_element(uint32_t seed, int dtype, uint32_t K, uint32_t row,
+                                            uint32_t col) {
+  const uint32_t ha = mix32(gemm_matrix_hash(seed, dtype, GEN_A) ^ row);
+  const uint32_t hb = gemm_matrix_hash(seed, dtype, GEN_B);
+  int32_t acc = gen_gemm_int(seed, dtype, GEN_C, row, col);
+  for (uint32_t k = 0; k < K; ++k) {
+    const int a = (int)((mix32(ha + k) >> 8) % 17u) - 8;  // gemm_int_of, the row hoisted
+    acc += a * gemm_int_of(hb, k, col);
+  }
+  return acc;
+}
+
+// a 16-bit operand of the GEMM as it lies in memory
+GH_HD inline uint16_t gemm_encode(int dtype, int value) {
+  return dtype == F16 ? f32_to_f16((float)value) : f32_to_bf16((float)value);
 }
 
 }  // namespace gh

@@ -373,14 +373,17 @@ def gpu_burn_in_load_seconds(annotations: Optional[Dict[str, str]]) -> Optional[
 
 
 def init_gpu_burn_in_startup_probe(ray_container: Container,
-                                   load_seconds: Optional[float] = None) -> None:
+                                   load_seconds: Optional[float] = None,
+                                   gemm: bool = False) -> None:
     """MI355X burn-in as a startupProbe (opt-in, annotation
     ``amd.com/gpu-burn-in: "true"`` on a GPU worker template): the HBM
     pattern sweep and the exact MFMA checks of
     ``python -m kuberay_amd.gpu.probe --deep`` must pass once before the
     kubelet starts the liveness and readiness probes, which stay as built.
     ``load_seconds`` (annotation ``amd.com/gpu-burn-in-load-seconds``) adds
-    the MFMA load and its time to the probe's timeout.
+    the MFMA load and its time to the probe's timeout; ``gemm`` (annotation
+    ``amd.com/gpu-burn-in-gemm: "true"``) adds the GEMM check, which is
+    milliseconds long and leaves the timeout alone.
     A user-supplied startupProbe is kept."""
     if ray_container.startup_probe is not None:
         return
@@ -389,6 +392,8 @@ def init_gpu_burn_in_startup_probe(ray_container: Container,
     if load_seconds is not None:
         command += f" --load-seconds {load_seconds:g}"
         timeout += math.ceil(load_seconds) + C.GPU_BURN_IN_LOAD_PROBE_OVERHEAD_SECONDS
+    if gemm:
+        command += " --gemm"
     probe = Probe(
         timeout_seconds=timeout,
         period_seconds=C.GPU_BURN_IN_PROBE_PERIOD_SECONDS,
@@ -825,7 +830,9 @@ def build_pod(
             C.GPU_BURN_IN_ANNOTATION_KEY, "").lower() == "true"
         if gpu_probe and burn_in:
             init_gpu_burn_in_startup_probe(
-                ray_container, gpu_burn_in_load_seconds(template.metadata.annotations))
+                ray_container, gpu_burn_in_load_seconds(template.metadata.annotations),
+                gemm=(template.metadata.annotations or {}).get(
+                    C.GPU_BURN_IN_GEMM_ANNOTATION_KEY, "").lower() == "true")
     return pod
 
 

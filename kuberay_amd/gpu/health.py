@@ -63,6 +63,9 @@ class HealthReport:
     mfma_load_clock_mhz: Optional[Dict[str, float]] = None
     mfma_load_faulty: Optional[List[str]] = None
     mfma_load_ok_by_dtype: Optional[Dict[str, bool]] = None
+    # GEMM check of the burn-in level; None unless it was asked for
+    gemm_exact: Optional[Dict[str, bool]] = None
+    gemm_faulty: Optional[List[str]] = None
 
 
 def _rocm_smi_ok() -> bool:
@@ -179,12 +182,40 @@ def _mfma_load(native, device: int, load_seconds: float, floors: Dict[str, float
     return ok, tflops, clock, faulty, problems
 
 
+GEMM_DTYPES = ("bf16", "f16")
+
+
+def _gemm_exact(native, device: int):
+    """The GEMM check at its default shape, once per 16-bit data type. Returns
+    (ok by data type, faulty, problems)."""
+    if not hasattr(native, "gemm_exact"):
+        return {}, [], ["gemm: asked for, but this native module has no gemm_exact"]
+    ok, faulty, problems = {}, [], []
+    for dtype in GEMM_DTYPES:
+        r = native.gemm_exact(device, dtype)
+        ok[dtype] = bool(r["ok"])
+        if ok[dtype]:
+            continue
+        faulty.extend(f"{dtype} {_cu_name(f, short=True)}" for f in r["faulty"])
+        problem = f"gemm {dtype} {r['m']}x{r['n']}x{r['k']}: {r['mismatches']} bad elements"
+        if r["first_bad"] is not None:
+            row, col, got, expected = r["first_bad"]
+            problem += f", first [{row}][{col}] got {got!r} expected {expected!r}"
+        if r["faulty"]:
+            problem += " on cu " + ", ".join(_cu_name(f) for f in r["faulty"][:4])
+            if len(r["faulty"]) > 4:
+                problem += f" and {len(r['faulty']) - 4} more tiles"
+        problems.append(problem)
+    return ok, faulty, problems
+
+
 def check_gpu_burn_in(device: int = 0,
                       hbm_fraction: float = DEFAULT_BURN_IN_HBM_FRACTION,
                       hbm_floor_gb_s: float = DEFAULT_HBM_FLOOR_GB_S,
                       require_cu_coverage: bool = False,
                       load_seconds: float = 0.0,
-                      mfma_floor_tflops: Optional[Dict[str, float]] = None) -> HealthReport:
+                      mfma_floor_tflops: Optional[Dict[str, float]] = None,
+                      gemm: bool = False) -> HealthReport:
     """Burn-in level: the full gate of ``check_gpu_health``, then the exact
     MFMA verification on the bf16, f16, fp8 and MXFP4 data paths, then a
     data-verifying pattern sweep over ``hbm_fraction`` of the free HBM, then
@@ -195,6 +226,10 @@ def check_gpu_burn_in(device: int = 0,
     busy on self-checking data for a quarter of that time per data type. A
     wrong element, or a rate under ``mfma_floor_tflops`` (by data type, over
     ``DEFAULT_MFMA_FLOOR_TFLOPS``), is unhealthy and named in ``detail``.
+    With ``gemm`` the GEMM check follows the CU sweep: one exact bf16 and one
+    exact f16 GEMM staged through LDS by direct-to-LDS loads and read back
+    with the transposed LDS read. A wrong element is unhealthy, and ``detail``
+    names the data type, the first bad element and the CU of its tile.
     Raises GpuHealthError on non-GPU hosts; ``detail`` names what failed."""
     if not gpu_node():
         raise GpuHealthError("not a GPU node (/dev/kfd missing)")
@@ -247,6 +282,14 @@ def check_gpu_burn_in(device: int = 0,
             problems.append(f"cu coverage {cu_covered}/{cu_total} after "
                             f"{sweep['rounds']} rounds")
             healthy = healthy and not require_cu_coverage
+    gemm_ok = gemm_faulty = None
+    if gemm:
+        try:
+            gemm_ok, gemm_faulty, gemm_problems = _gemm_exact(native, device)
+        except RuntimeError as e:
+            return _hip_failure(e, rocm_ok)
+        problems.extend(gemm_problems)
+        healthy = healthy and not gemm_problems
     load_ok = load_by_dtype = load_tflops = load_clock = load_faulty = None
     if load_seconds > 0.0:
         try:
@@ -273,6 +316,7 @@ def check_gpu_burn_in(device: int = 0,
         mfma_load_ok=load_ok, mfma_load_tflops=load_tflops,
         mfma_load_clock_mhz=load_clock, mfma_load_faulty=load_faulty,
         mfma_load_ok_by_dtype=load_by_dtype,
+        gemm_exact=gemm_ok, gemm_faulty=gemm_faulty,
     )
 
 

@@ -14,6 +14,11 @@ load to the burn-in level: S seconds of self-checking MFMA on every matrix
 pipe, a quarter per data type, with a TFLOP/s floor (annotation
 ``amd.com/gpu-burn-in-load-seconds``). Its fields appear in the output only
 when it ran.
+
+``--deep --gemm`` adds the GEMM check (annotation
+``amd.com/gpu-burn-in-gemm``): one exact bf16 and one exact f16 GEMM through
+direct-to-LDS loads, transposed LDS reads and MFMA, milliseconds long. Its
+fields appear in the output only when it was asked for.
 """
 from __future__ import annotations
 
@@ -49,7 +54,12 @@ def main(argv=None) -> int:
                         metavar="DTYPE=N",
                         help="with --load-seconds: TFLOP/s floor of one data "
                              "type (bf16, f16, fp8, mxfp4); may be repeated")
+    parser.add_argument("--gemm", action="store_true",
+                        help="with --deep: the exact GEMM check through "
+                             "direct-to-LDS loads and transposed LDS reads")
     args = parser.parse_args(argv)
+    if args.gemm and not args.deep:
+        parser.error("--gemm needs --deep")
     if args.load_seconds and not args.deep:
         parser.error("--load-seconds needs --deep")
     if args.mfma_floor_tflops and not args.load_seconds:
@@ -71,6 +81,8 @@ def main(argv=None) -> int:
                 parser.error(f"--mfma-floor-tflops wants DTYPE=N with DTYPE one of "
                              f"{', '.join(MFMA_LOAD_DTYPES)} and N >= 0, got {item!r}")
         load = {"load_seconds": args.load_seconds, "mfma_floor_tflops": floors or None}
+    if args.gemm:
+        load["gemm"] = True
 
     try:
         if args.deep:
@@ -106,6 +118,8 @@ def main(argv=None) -> int:
                            mfma_load_tflops=report.mfma_load_tflops,
                            mfma_load_clock_mhz=report.mfma_load_clock_mhz,
                            mfma_load_faulty=report.mfma_load_faulty)
+            if args.gemm:
+                out.update(gemm_exact=report.gemm_exact, gemm_faulty=report.gemm_faulty)
             print(json.dumps(out))
         else:
             cu = (f" cu_total={report.cu_total} cu_covered={report.cu_covered} "
@@ -115,6 +129,8 @@ def main(argv=None) -> int:
                        f"mfma_load_tflops={report.mfma_load_tflops} "
                        f"mfma_load_clock_mhz={report.mfma_load_clock_mhz} "
                        f"mfma_load_faulty={report.mfma_load_faulty}")
+            if args.gemm:
+                cu += f" gemm_exact={report.gemm_exact} gemm_faulty={report.gemm_faulty}"
             print(f"healthy={report.healthy} mfma_ok={report.mfma_ok} "
                   f"hbm_gb_s={report.hbm_gb_s} rocm_smi_ok={report.rocm_smi_ok} "
                   f"mfma_exact={report.mfma_exact} "

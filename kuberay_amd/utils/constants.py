@@ -246,6 +246,10 @@ GPU_BURN_IN_LOAD_MAX_SECONDS = 60.0
 # position, right after another probe (8.5 s), it is 0.3 s at the most.
 # Measurement: docs/benchmarks.md, "MFMA load".
 GPU_BURN_IN_LOAD_PROBE_OVERHEAD_SECONDS = 20
+# Pod-template annotation: "true" on a template that also carries
+# amd.com/gpu-burn-in: "true" adds the GEMM check to the burn-in (``--gemm``).
+# The check is milliseconds long, so the startup probe's timeout stays.
+GPU_BURN_IN_GEMM_ANNOTATION_KEY = "amd.com/gpu-burn-in-gemm"
 
 # Device nodes every ROCm container needs (AMD k8s device plugin mounts these
 # automatically when amd.com/gpu is requested; we also support explicit
