@@ -167,7 +167,10 @@
 //                    (cu_seen says how many were). Test hooks:
 //                    gemm_exact(inject=), an xor into one 16-bit element of A
 //                    or B in device memory between the fill and the GEMM;
-//                    debug_gemm_dump (the raw A, B, C and D of the same code
+//                    gemm_exact(lds_inject=), an xor into one 16-bit LDS word
+//                    of one workgroup after a stage has landed (an
+//                    instantiation of its own; the production kernels do not
+//                    carry it); debug_gemm_dump (the raw A, B, C and D of the same code
 //                    path); debug_lds_tr_dump; gemm_operand.
 //
 // What must agree between host and device (pattern, generators, encoders,
@@ -1845,6 +1848,9 @@ static py::dict device_info(int device) {
   d["name"] = std::string(prop.name);
   d["gcn_arch"] = std::string(prop.gcnArchName);
   d["total_mem_gb"] = (double)prop.totalGlobalMem / (1024.0 * 1024.0 * 1024.0);
+  size_t free_b = 0, total_b = 0;
+  HIP_CHECK(hipMemGetInfo(&free_b, &total_b));
+  d["free_mem_gb"] = (double)free_b / (1024.0 * 1024.0 * 1024.0);  // right now: others share it
   d["multi_processor_count"] = prop.multiProcessorCount;
   d["warp_size"] = prop.warpSize;
   d["clock_mhz"] = prop.clockRate / 1000;
@@ -2337,6 +2343,26 @@ static std::optional<ghgemm::Inject> checked_gemm_inject(const inject_gemm_t& in
   return inj;
 }
 
+// (tile = tile_row * tiles_n + tile_col, stage, even byte offset within the
+// stage, 16-bit xor mask); the tile and the stage are checked against the shape
+// by run_gemm_exact
+typedef std::optional<std::tuple<int64_t, int64_t, int64_t, int64_t>> lds_inject_gemm_t;
+
+static std::optional<ghgemm::LdsInject> checked_gemm_lds_inject(const lds_inject_gemm_t& in) {
+  if (!in) return std::nullopt;
+  const auto& [tile, stage, offset, mask] = *in;
+  if (mask <= 0 || mask > 0xFFFF) throw py::value_error("xor mask must be a non-zero 16-bit value");
+  ghgemm::LdsInject inj;
+  inj.tile = checked_index(tile, 1ull << 32, "LDS fault tile");
+  inj.stage = checked_index(stage, 1ull << 32, "LDS fault stage");
+  inj.offset = checked_index(offset, 1ull << 32, "LDS fault offset");
+  inj.mask = (uint32_t)mask;
+  return inj;
+}
+
+// the dump's limit: what m = n = k = 4096 takes, A and B and C and D together
+constexpr uint64_t kGemmDumpMaxBytes = 192ull << 20;
+
 static py::dict gemm_exact_dict(const ghgemm::Result& r) {
   py::dict d;
   py::list faulty;
@@ -2369,23 +2395,32 @@ static py::dict gemm_exact_dict(const ghgemm::Result& r) {
 }
 
 static py::dict gemm_exact(int device, const std::string& dtype, int64_t m, int64_t n, int64_t k,
-                           uint32_t seed, inject_gemm_t inject) {
+                           uint32_t seed, inject_gemm_t inject, lds_inject_gemm_t lds_inject) {
   const int dt = parse_dtype(dtype);
   const std::optional<ghgemm::Inject> inj = checked_gemm_inject(inject);
+  const std::optional<ghgemm::LdsInject> lds = checked_gemm_lds_inject(lds_inject);
   use_device(device);
-  return gemm_exact_dict(ghgemm::run_gemm_exact(dt, m, n, k, seed, inj ? &*inj : nullptr));
+  return gemm_exact_dict(ghgemm::run_gemm_exact(dt, m, n, k, seed, inj ? &*inj : nullptr, nullptr,
+                                                lds ? &*lds : nullptr));
 }
 
 // test hook: the raw A, B, C and D of the same fill, inject and GEMM
 static py::dict debug_gemm_dump(int device, const std::string& dtype, int64_t m, int64_t n,
-                                int64_t k, uint32_t seed, inject_gemm_t inject) {
+                                int64_t k, uint32_t seed, inject_gemm_t inject,
+                                lds_inject_gemm_t lds_inject) {
   const int dt = parse_dtype(dtype);
   const std::optional<ghgemm::Inject> inj = checked_gemm_inject(inject);
-  if (m > 4096 || n > 4096 || k > 4096)
-    throw py::value_error("the dump takes m, n and k of at most 4096");
+  const std::optional<ghgemm::LdsInject> lds = checked_gemm_lds_inject(lds_inject);
+  // bounded by bytes and not by side, so that one tile of the deepest K can be
+  // dumped; shapes run_gemm_exact refuses are left to it
+  const int64_t side = 65536;
+  if (m > 0 && n > 0 && k > 0 && m <= side && n <= side && k <= side &&
+      2 * (uint64_t)m * k + 2 * (uint64_t)k * n + 8 * (uint64_t)m * n > kGemmDumpMaxBytes)
+    throw py::value_error("the dump takes at most 192 MiB of A, B, C and D together");
   use_device(device);
   ghgemm::Dump dump;
-  (void)ghgemm::run_gemm_exact(dt, m, n, k, seed, inj ? &*inj : nullptr, &dump);
+  (void)ghgemm::run_gemm_exact(dt, m, n, k, seed, inj ? &*inj : nullptr, &dump,
+                               lds ? &*lds : nullptr);
   py::dict d;
   d["a"] = py::bytes(dump.a);
   d["b"] = py::bytes(dump.b);
@@ -2494,10 +2529,12 @@ PYBIND11_MODULE(gpuhealth, m) {
   m.attr("GEMM_WORKGROUPS_PER_CU") = ghgemm::kWorkgroupsPerCu;
   m.def("gemm_exact", &gemm_exact, py::arg("device") = 0, py::arg("dtype") = "bf16",
         py::arg("m") = 0, py::arg("n") = 0, py::arg("k") = 0,
-        py::arg("seed") = gh::kDefaultSeed, py::arg("inject") = py::none());
+        py::arg("seed") = gh::kDefaultSeed, py::arg("inject") = py::none(),
+        py::arg("lds_inject") = py::none());
   m.def("debug_gemm_dump", &debug_gemm_dump, py::arg("device") = 0, py::arg("dtype") = "bf16",
         py::arg("m") = 64, py::arg("n") = 64, py::arg("k") = 64,
-        py::arg("seed") = gh::kDefaultSeed, py::arg("inject") = py::none());
+        py::arg("seed") = gh::kDefaultSeed, py::arg("inject") = py::none(),
+        py::arg("lds_inject") = py::none());
   m.def("debug_lds_tr_dump", &debug_lds_tr_dump, py::arg("device") = 0);
   m.def("gemm_operand", &gemm_operand, py::arg("dtype"), py::arg("which"), py::arg("row"),
         py::arg("col"), py::arg("seed") = gh::kDefaultSeed);

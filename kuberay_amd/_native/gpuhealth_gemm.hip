@@ -183,8 +183,16 @@ __device__ inline void gemm_issue_stage(const GemmArgs& g, uint32_t m0, uint32_t
 template <int DT> struct GemmFrag { typedef frag_ab_t type; };
 template <> struct GemmFrag<gh::F16> { typedef frag_f16_t type; };
 
-template <int DT>
-__global__ __launch_bounds__(kGemmThreads) void gemm_exact_kernel(GemmArgs g) {
+// HOOK is the test hook of run_gemm_exact(lds_inject), an instantiation of its
+// own: in the production kernels (HOOK = false) every line under
+// if constexpr (HOOK) is absent and the second argument is an empty struct.
+struct NoHook {};
+template <bool HOOK> struct GemmHook { typedef NoHook type; };
+template <> struct GemmHook<true> { typedef LdsInject type; };
+
+template <int DT, bool HOOK>
+__global__ __launch_bounds__(kGemmThreads) void gemm_exact_kernel(
+    GemmArgs g, typename GemmHook<HOOK>::type hook) {
   static_assert(DT == gh::BF16 || DT == gh::F16, "the 16-bit paths only");
   typedef typename GemmFrag<DT>::type frag_t;
   __shared__ __attribute__((aligned(16))) unsigned char lds_raw[kGemmLdsBytes];
@@ -214,6 +222,20 @@ __global__ __launch_bounds__(kGemmThreads) void gemm_exact_kernel(GemmArgs g) {
   for (uint32_t s = 0; s < stages; ++s) {
     GH_LDS unsigned char* a_lds = lds + (s & 1u) * kGemmStageBytes;
     GH_LDS unsigned char* b_lds = a_lds + kGemmOperandBytes;
+    if constexpr (HOOK) {
+      // Stage s is visible to everybody (the barrier before this iteration)
+      // and nobody has read it yet: one thread of the chosen workgroup xors
+      // one 16-bit word of it, a plain LDS load and store, and a barrier that
+      // only this instantiation has publishes the change. The condition is
+      // uniform over the workgroup.
+      if (blockIdx.x == hook.tile && s == hook.stage) {
+        if (threadIdx.x == 0) {
+          GH_LDS uint16_t* word = (GH_LDS uint16_t*)(a_lds + hook.offset);
+          *word = (uint16_t)(*word ^ hook.mask);
+        }
+        __syncthreads();
+      }
+    }
     if (s + 1 < stages)
       gemm_issue_stage(g, m0, n0, (s + 1) * gh::kGemmTile,
                        lds + ((s + 1) & 1u) * kGemmStageBytes, wave, lane);
@@ -320,7 +342,7 @@ static std::string device_bytes(const void* ptr, size_t bytes) {
 }  // namespace
 
 Result run_gemm_exact(int dtype, int64_t m_in, int64_t n_in, int64_t k_in, uint32_t seed,
-                      const Inject* inject, Dump* dump) {
+                      const Inject* inject, Dump* dump, const LdsInject* lds_inject) {
   if (dtype != gh::BF16 && dtype != gh::F16)
     throw std::invalid_argument("the GEMM check runs bf16 and f16 only");
   int device = 0, cu_total = 0;
@@ -345,6 +367,12 @@ Result run_gemm_exact(int dtype, int64_t m_in, int64_t n_in, int64_t k_in, uint3
     const bool is_a = inject->is_a;
     if (inject->row >= (is_a ? m : k) || inject->col >= (is_a ? k : n))
       throw std::invalid_argument("injected element is outside the matrix");
+  }
+  if (lds_inject) {
+    if (lds_inject->tile >= tiles || lds_inject->stage >= k / gh::kGemmTile)
+      throw std::invalid_argument("LDS fault names a tile or a stage the GEMM does not have");
+    if (lds_inject->offset >= kGemmStageBytes || lds_inject->offset % 2)
+      throw std::invalid_argument("LDS fault offset must be an even byte offset within a stage");
   }
 
   DeviceScope scope;
@@ -382,10 +410,18 @@ Result run_gemm_exact(int dtype, int64_t m_in, int64_t n_in, int64_t k_in, uint3
   const GemmArgs args{d_a, d_b, d_c, d_d, d_where, n, k, tiles_n};
   hipEvent_t t0 = scope.event(), t1 = scope.event();
   HIP_CHECK(hipEventRecord(t0, 0));
-  if (dtype == gh::BF16)
-    hipLaunchKernelGGL(gemm_exact_kernel<gh::BF16>, dim3(tiles), dim3(kGemmThreads), 0, 0, args);
+  if (lds_inject && dtype == gh::BF16)
+    hipLaunchKernelGGL((gemm_exact_kernel<gh::BF16, true>), dim3(tiles), dim3(kGemmThreads), 0,
+                       0, args, *lds_inject);
+  else if (lds_inject)
+    hipLaunchKernelGGL((gemm_exact_kernel<gh::F16, true>), dim3(tiles), dim3(kGemmThreads), 0,
+                       0, args, *lds_inject);
+  else if (dtype == gh::BF16)
+    hipLaunchKernelGGL((gemm_exact_kernel<gh::BF16, false>), dim3(tiles), dim3(kGemmThreads), 0,
+                       0, args, NoHook{});
   else
-    hipLaunchKernelGGL(gemm_exact_kernel<gh::F16>, dim3(tiles), dim3(kGemmThreads), 0, 0, args);
+    hipLaunchKernelGGL((gemm_exact_kernel<gh::F16, false>), dim3(tiles), dim3(kGemmThreads), 0,
+                       0, args, NoHook{});
   HIP_CHECK(hipGetLastError());
   HIP_CHECK(hipEventRecord(t1, 0));
   hipLaunchKernelGGL(gemm_check_kernel, dim3(tiles * 16), dim3(256), 0, 0, d_d, dtype, seed, n,

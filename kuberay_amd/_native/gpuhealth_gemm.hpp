@@ -29,6 +29,14 @@ struct Inject {
   uint32_t row = 0, col = 0, mask = 0;
 };
 
+// Test hook: an xor into one 16-bit word of the LDS of one workgroup, after
+// stage `stage` of it has been staged and before its first read. tile is the
+// workgroup (tile_row * tiles_n + tile_col), offset the even byte offset within
+// the stage: A's 8 KiB, then B's.
+struct LdsInject {
+  uint32_t tile = 0, stage = 0, offset = 0, mask = 0;
+};
+
 struct FaultyTile {
   uint32_t tile_row, tile_col, key;  // key: gh::location_key of where it ran
   TileStats stats;
@@ -53,11 +61,12 @@ struct Dump {
 // the smallest multiple of 64 that gives every CU kWorkgroupsPerCu workgroups.
 // Throws std::invalid_argument for m, n or k that is no positive multiple of
 // 64, k above gh::kGemmMaxK (exactness) or m, n above gh::kGemmMaxMN (a bound
-// on what one call allocates), a data type other than bf16 / f16 and an
-// injected element outside its matrix; std::runtime_error for a failing HIP
-// call. Single-shot: one fill, one GEMM launch (timed with events), one check.
+// on what one call allocates), a data type other than bf16 / f16, an
+// injected element outside its matrix and an LDS fault outside the tiles, the
+// stages or a stage's 16 KiB; std::runtime_error for a failing HIP call. Single-shot: one fill, one GEMM launch (timed with events), one check.
 Result run_gemm_exact(int dtype, int64_t m, int64_t n, int64_t k, uint32_t seed,
-                      const Inject* inject = nullptr, Dump* dump = nullptr);
+                      const Inject* inject = nullptr, Dump* dump = nullptr,
+                      const LdsInject* lds_inject = nullptr);
 
 // one wave's transposed LDS read of words that hold their own index: 64 x 4
 std::vector<std::vector<int>> run_debug_lds_tr_dump();

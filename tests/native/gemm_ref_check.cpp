@@ -36,6 +36,18 @@ int main() {
                      gh::gen_gemm_int(seed, dt, gh::GEN_B, kk, c);
             CHECK(sum == gh::gemm_reference_element(seed, dt, k, r, c));
           }
+      // the table tests/test_gemm_ref.py holds tests/gemm_model.py against:
+      // generator values at near and far indices, reference elements
+      for (uint32_t which : {(uint32_t)gh::GEN_A, (uint32_t)gh::GEN_B, (uint32_t)gh::GEN_C})
+        for (uint32_t r : {0u, 1u, 63u, 64u, 1471u, 32767u, 65535u, 0xFFFFFF03u})
+          for (uint32_t c : {0u, 1u, 65u, 1023u, 65472u, 65535u, 0x80000007u})
+            std::printf("gen %u %d %u %u %u %d\n", seed, dt, which, r, c,
+                        gh::gen_gemm_int(seed, dt, which, r, c));
+      for (uint32_t k : {64u, 192u, 1024u})
+        for (uint32_t r : {0u, 127u, 32767u})
+          for (uint32_t c : {0u, 191u, 65535u})
+            std::printf("ref %u %d %u %u %u %d\n", seed, dt, k, r, c,
+                        gh::gemm_reference_element(seed, dt, k, r, c));
     }
   static_assert(64ull * gh::kGemmMaxK + 8 < (1ull << 24), "every sum is exact in fp32");
   std::printf("gemm_ref_check OK\n");

@@ -1,8 +1,13 @@
 """The burn-in's GEMM check on the device against numpy in float64; the operands
 are small integers, so every comparison is exact. Shapes: one stage, the first
-buffer swap, a reused buffer, several workgroups of a non-square matrix."""
+buffer swap, a reused buffer, several workgroups of a non-square matrix; then
+the edges, against tests/gemm_model.py: the default shape (every CU, several
+workgroups per CU, 16 stages), the deepest K, the widest and the tallest grid
+of tiles, a D of 4 GiB, a second seed, and where the faulty tiles ran."""
 import numpy as np
 import pytest
+
+import gemm_model as gm
 
 pytestmark = pytest.mark.gpu
 
@@ -113,3 +118,149 @@ def test_transposed_read_lane_map(native):
     got = np.array(native.debug_lds_tr_dump(0))
     lane, e = np.arange(64)[:, None], np.arange(4)[None, :]
     assert np.array_equal(got, 4 * (lane & ~15) + 16 * e + (lane & 15))
+
+
+# ---------------------------------------------------------------------------
+# shape and seed edges, against the numpy model of tests/gemm_model.py
+# ---------------------------------------------------------------------------
+def _unpack(dtype, raw, m, n, k):
+    a = gm.decode(dtype, np.frombuffer(raw["a"], np.uint16)).reshape(m, k)
+    b = gm.decode(dtype, np.frombuffer(raw["b"], np.uint16)).reshape(k, n)
+    c, d = (np.frombuffer(raw[x], np.float32).reshape(m, n) for x in "cd")
+    return a, b, c, d
+
+
+def _assert_model_dump(dtype, seed, raw, m, n, k):
+    """A, B and C are the generator's everywhere and D is the float64 product."""
+    a, b, c, d = _unpack(dtype, raw, m, n, k)
+    for which, mat in (("a", a), ("b", b), ("c", c)):
+        assert np.array_equal(mat, gm.operand_matrix(dtype, seed, which, *mat.shape)), which
+    ref = a @ b + c
+    assert np.abs(ref).max() < 2 ** 24
+    assert np.array_equal(d, ref)
+    return ref
+
+
+def _assert_line_fault(native, dtype, m, n, k, case):
+    """A memory-side fault at a shape too large to dump: the report against the
+    rule, the reference for the one affected line from the generator alone."""
+    v = gm.line_verdict(dtype, gm.DEFAULT_SEED, m, n, k, case)
+    assert v.undecided == 0 and v.bad.any()
+    r = native.gemm_exact(0, dtype, m, n, k, inject=case)
+    tiles = v.tiles()
+    assert r["ok"] is False and r["mismatches"] == int(v.bad.sum())
+    assert [f["tile"] for f in r["faulty"]] == sorted(tiles)
+    assert all((f["mismatches"], f["first_bad"]) == tiles[f["tile"]] for f in r["faulty"])
+    row, col, got, expected = r["first_bad"]
+    assert (row, col) == v.first_bad()
+    assert expected == gm.reference_element(dtype, gm.DEFAULT_SEED, k, row, col)
+    assert v.got_matches(row, col, got) and got != expected
+    return r
+
+
+def _nonzero_k(dtype, operand, line, lo, hi):
+    """The first k in lo..hi - 1 at which A[line][k] / B[k][line] is not 0."""
+    if operand == "a":
+        values = gm.operand_matrix(dtype, gm.DEFAULT_SEED, "a", 1, hi - lo, line, lo)[0]
+    else:
+        values = gm.operand_matrix(dtype, gm.DEFAULT_SEED, "b", hi - lo, 1, lo, line)[:, 0]
+    return lo + int(np.flatnonzero(values)[0])
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+def test_default_shape_against_numpy(native, dtype):
+    """What the probe runs: two workgroups or more per CU at non-zero LDS bases,
+    every CU, 16 stages per workgroup."""
+    r = native.gemm_exact(0, dtype)
+    m, n, k = r["m"], r["n"], r["k"]
+    assert r["ok"] is True and k == 1024 and r["workgroups"] >= 2 * r["cu_total"]
+    assert 1 <= r["cu_seen"] <= r["cu_total"]
+    _assert_model_dump(dtype, gm.DEFAULT_SEED, native.debug_gemm_dump(0, dtype, m, n, k), m, n, k)
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+def test_deepest_k(native, dtype):
+    """K = 65536, the exactness limit: 1024 stages, the buffer parity all the way;
+    then a fault in the last stage."""
+    m, n, k = 64, 64, 65536
+    ref = _assert_model_dump(dtype, gm.DEFAULT_SEED, native.debug_gemm_dump(0, dtype, m, n, k),
+                             m, n, k)
+    print(f"{dtype}: max |D| at K = 65536 is {np.abs(ref).max():.0f}")
+    assert native.gemm_exact(0, dtype, m, n, k)["ok"] is True
+    kk = _nonzero_k(dtype, "a", 61, 65472, 65536)
+    assert 65472 <= kk < 65536
+    r = _assert_line_fault(native, dtype, m, n, k, ("a", 61, kk, 0x8000))
+    assert [f["tile"] for f in r["faulty"]] == [(0, 0)]
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+def test_widest_and_tallest_grid(native, dtype):
+    """tiles_n = 1024 and its tall mirror, clean and with a fault in the last tile."""
+    wide, tall = (64, 65536, 64), (65536, 64, 64)
+    for shape in (wide, tall):
+        r = native.gemm_exact(0, dtype, *shape)
+        assert (r["ok"], r["mismatches"], r["faulty"], r["workgroups"]) == (True, 0, [], 1024)
+    col = 65536 - 3
+    r = _assert_line_fault(native, dtype, *wide, ("b", _nonzero_k(dtype, "b", col, 32, 64), col, 0x8000))
+    assert [f["tile"] for f in r["faulty"]] == [(0, 1023)]
+    row = 65536 - 3
+    r = _assert_line_fault(native, dtype, *tall, ("a", row, _nonzero_k(dtype, "a", row, 32, 64), 0x8000))
+    assert [f["tile"] for f in r["faulty"]] == [(1023, 0)]
+
+
+@pytest.mark.parametrize("m", [32768, 65536])
+def test_d_of_4_gib_and_beyond(native, m):
+    """m x 32768 x 64. At m = 32768 C and D are 4 GiB each: byte offsets into them
+    reach 2^32 - 4, past what a signed 32-bit offset holds. At m = 65536 they are
+    8 GiB and the byte offsets pass 2^32. (The element indices stay below 2^32 at
+    every shape the check accepts, so it is the 64-bit byte addressing that is
+    pinned here.) Clean, then a fault in A's last row: the last tile row, all
+    512 tile columns."""
+    need = 4 * (m // 32768) * 4  # C and D, and as much again to be safe, in GiB
+    free = native.device_info(0)["free_mem_gb"]
+    if free < need:
+        pytest.skip(f"{free:.1f} GiB free on the device; the case wants {need} GiB to be safe")
+    n, row = 32768, m - 1
+    r = native.gemm_exact(0, "bf16", m, n, 64)
+    assert (r["ok"], r["mismatches"], r["faulty"], r["workgroups"]) == (True, 0, [], m // 64 * 512)
+    r = _assert_line_fault(native, "bf16", m, n, 64, ("a", row, _nonzero_k("bf16", "a", row, 32, 64), 0x8000))
+    assert [f["tile"] for f in r["faulty"]] == [(m // 64 - 1, t) for t in range(512)]
+    assert r["first_bad"][0] == row and (row * n * 4 >= 1 << 32) is (m == 65536)
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+def test_second_seed(native, dtype):
+    m, n, k = 128, 192, 128
+    _assert_model_dump(dtype, gm.SEED2, native.debug_gemm_dump(0, dtype, m, n, k, seed=gm.SEED2),
+                       m, n, k)
+    first = _unpack(dtype, native.debug_gemm_dump(0, dtype, m, n, k), m, n, k)[0]
+    assert not np.array_equal(first, gm.operand_matrix(dtype, gm.SEED2, "a", m, k))  # another matrix
+    for which, (rows, cols) in (("a", (m, k)), ("b", (k, n)), ("c", (m, n))):
+        model = gm.operand_matrix(dtype, gm.SEED2, which, rows, cols)
+        for r in range(0, rows, 17):
+            for col in range(0, cols, 13):
+                assert native.gemm_operand(dtype, which, r, col, seed=gm.SEED2) == model[r, col]
+        assert native.gemm_operand(dtype, which, 0xFFFFFF03, 0x80000007, seed=gm.SEED2) == \
+            gm.operand_matrix(dtype, gm.SEED2, which, 1, 1, 0xFFFFFF03, 0x80000007)[0, 0]
+    r = native.gemm_exact(0, dtype, m, n, k, seed=gm.SEED2)
+    assert (r["ok"], r["mismatches"], r["faulty"], r["first_bad"]) == (True, 0, [], None)
+
+
+def test_faulty_tiles_ran_where_the_sweep_has_been(native):
+    """The location of a faulty tile is a CU of this device: one of the places a
+    saturating CU sweep reports in its coverage map."""
+    sweep = native.cu_sweep()
+    if sweep["cu_covered"] < sweep["cu_total"]:
+        sweep = native.cu_sweep(max_rounds=32)
+    # an element of A that is 1 or -1 becomes Inf: its whole row of D is bad, three tiles
+    row, col = gm.find_element(gm.operand_matrix("f16", gm.DEFAULT_SEED, "a", 128, 128), 1)
+    r = native.gemm_exact(0, "f16", 128, 192, 128, inject=("a", row, col, 0x4000))
+    assert len(r["faulty"]) == 3 and all(f["mismatches"] == 64 for f in r["faulty"])
+    for f in r["faulty"]:
+        assert all(isinstance(f[key], int) and f[key] >= 0 for key in ("xcc", "se", "sh", "cu"))
+    if sweep["cu_covered"] < sweep["cu_total"]:
+        pytest.skip(f"the CU sweep covered {sweep['cu_covered']} of {sweep['cu_total']} CUs: "
+                    "its map cannot vouch for every location")
+    known = {(l["xcc"], l["se"], l["sh"], l["cu"]) for l in sweep["locations"]}
+    assert len(known) == sweep["cu_total"]
+    assert all((f["xcc"], f["se"], f["sh"], f["cu"]) in known for f in r["faulty"])
