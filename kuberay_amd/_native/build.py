@@ -3,7 +3,8 @@ live next to the sources so it travels to GPU boxes with the repo snapshot).
 
 Extensions:
   * gpuhealth  — HIP/gfx950 on-device health probes and burn-in
-                 (gpuhealth.hip and gpuhealth_gemm.hip over gpuhealth_ref.hpp)
+                 (gpuhealth.hip, gpuhealth_gemm.hip and gpuhealth_gemm_narrow.hip
+                 over gpuhealth_ref.hpp)
   * engine     — C++ control-plane core: object cache + indices + native
                  JSON encoding and decoding and model-tree copies (engine.cpp
                  bindings over store_core.hpp, json_decode.hpp and
@@ -44,24 +45,27 @@ def _needs_rebuild(src: Path, out: Path, *deps: Path) -> bool:
 
 def build_gpuhealth(force: bool = False) -> Path:
     src = HERE / "gpuhealth.hip"
-    gemm_src = HERE / "gpuhealth_gemm.hip"
+    gemm_srcs = [HERE / "gpuhealth_gemm.hip", HERE / "gpuhealth_gemm_narrow.hip"]
     out = HERE / f"gpuhealth{_ext_suffix()}"
-    if not force and not _needs_rebuild(src, out, gemm_src, HERE / "gpuhealth_ref.hpp",
-                                        HERE / "gpuhealth_gemm.hpp"):
+    if not force and not _needs_rebuild(src, out, *gemm_srcs, HERE / "gpuhealth_ref.hpp",
+                                        HERE / "gpuhealth_gemm.hpp",
+                                        HERE / "gpuhealth_gemm_device.hpp"):
         return out
     common = [HIPCC, f"--offload-arch={GFX_ARCH}", "-O3", "-std=c++17", "-fPIC"]
     with tempfile.TemporaryDirectory() as tmp:
-        # The GEMM check's kernels are a translation unit of their own, built
+        # The GEMM checks' kernels are translation units of their own, built
         # with packed fp32 arithmetic (v_pk_*_f32) disabled for the device code
         # (the reason is at the top of gpuhealth_gemm.hip); the host pass of
-        # that one compile does not know the feature and says so in a warning.
+        # those compiles does not know the feature and says so in a warning.
         # gpuhealth.hip is compiled with the flags it always had.
-        obj, gemm_obj = str(Path(tmp) / "gpuhealth.o"), str(Path(tmp) / "gpuhealth_gemm.o")
-        subprocess.run([*common, "-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops",
-                        "-c", str(gemm_src), "-o", gemm_obj], check=True)
+        obj = str(Path(tmp) / "gpuhealth.o")
+        gemm_objs = [str(Path(tmp) / f"{gemm_src.stem}.o") for gemm_src in gemm_srcs]
+        for gemm_src, gemm_obj in zip(gemm_srcs, gemm_objs):
+            subprocess.run([*common, "-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops",
+                            "-c", str(gemm_src), "-o", gemm_obj], check=True)
         subprocess.run([*common, *_pybind11_includes(), "-c", str(src), "-o", obj],
                        check=True)
-        subprocess.run([HIPCC, f"--offload-arch={GFX_ARCH}", "-shared", "-fPIC", obj, gemm_obj,
+        subprocess.run([HIPCC, f"--offload-arch={GFX_ARCH}", "-shared", "-fPIC", obj, *gemm_objs,
                         "-o", str(out)], check=True)
     return out
 

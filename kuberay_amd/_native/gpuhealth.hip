@@ -159,9 +159,8 @@
 //                    Cannot show: A and B of this size are served largely from
 //                    L2 / MALL after the fill's first touch, so HBM proper
 //                    stays the pattern sweep's job; the low mantissa bits of
-//                    the operands are still never set; fp8 and MXFP4 are not
-//                    staged through LDS (they need the ..._tr_b8 / ..._tr_b4
-//                    reads and scale staging); nothing here is sustained, one
+//                    the operands are still never set; fp8 and MXFP4 are
+//                    gemm_narrow_exact's; nothing here is sustained, one
 //                    launch of microseconds at whatever clock the device is
 //                    at; a CU the dispatcher gave no workgroup is not covered
 //                    (cu_seen says how many were). Test hooks:
@@ -172,11 +171,28 @@
 //                    instantiation of its own; the production kernels do not
 //                    carry it); debug_gemm_dump (the raw A, B, C and D of the same code
 //                    path); debug_lds_tr_dump; gemm_operand.
+//   * gemm_narrow_exact — opt-in, single-shot, an entry point of its own: the
+//                    same GEMM for fp8 (OCP e4m3, mfma_f32_16x16x32_fp8_fp8)
+//                    and MXFP4 (e2m1 with E8M0 scales,
+//                    mfma_scale_f32_16x16x128_f8f6f4), tiled and staged the
+//                    same way; bytes and nibbles go global -> LDS without a
+//                    VGPR, B comes out of LDS through ds_read_b64_tr_b8 /
+//                    ds_read_b64_tr_b4 (lane maps measured with
+//                    debug_lds_tr_dump(bits=8 / 4)), the MX scales are plain
+//                    byte loads from device memory. K is a multiple of 128
+//                    (fp8, up to 65536) or 256 (mxfp4, up to 4096, the
+//                    exactness bound of gpuhealth_ref.hpp). Cannot show:
+//                    scale staging through LDS, subnormal or non-finite fp8
+//                    operands, bit 0 of an e4m3 operand. Test hooks:
+//                    gemm_narrow_exact(inject=) into A, B, SA or SB in device
+//                    memory, debug_gemm_narrow_dump, gemm_narrow_operand.
+//                    Details: gpuhealth_gemm_narrow.hip.
 //
 // What must agree between host and device (pattern, generators, encoders,
 // reference) is in gpuhealth_ref.hpp. The kernels of gemm_exact ("Burn-in,
-// part 5") and their host code are in gpuhealth_gemm.hip, a translation unit of
-// its own (the reason is at its top); this file binds them.
+// part 5") and their host code are in gpuhealth_gemm.hip, those of
+// gemm_narrow_exact ("part 6") in gpuhealth_gemm_narrow.hip, translation units
+// of their own (the reason is at the top of the first); this file binds them.
 //
 // Build: hipcc --offload-arch=gfx950 (see kuberay_amd/_native/build.py).
 // Wavefront width is 64 on CDNA4 — all wave math below hard-codes 64.
@@ -2429,9 +2445,12 @@ static py::dict debug_gemm_dump(int device, const std::string& dtype, int64_t m,
   return d;
 }
 
-static std::vector<std::vector<int>> debug_lds_tr_dump(int device) {
+// bits = 16: ds_read_b64_tr_b16, words that hold their own index. bits = 8 and
+// 4: the narrow check's reads, the source of every output element.
+static std::vector<std::vector<int>> debug_lds_tr_dump(int device, int bits) {
+  if (bits != 16 && bits != 8 && bits != 4) throw py::value_error("bits must be 16, 8 or 4");
   use_device(device);
-  return ghgemm::run_debug_lds_tr_dump();
+  return bits == 16 ? ghgemm::run_debug_lds_tr_dump() : ghgemm::run_debug_lds_tr_dump_narrow(bits);
 }
 
 static int gemm_operand(const std::string& dtype, const std::string& which, int64_t row,
@@ -2444,6 +2463,84 @@ static int gemm_operand(const std::string& dtype, const std::string& which, int6
   return gh::gen_gemm_int(seed, dt, which == "a" ? gh::GEN_A : which == "b" ? gh::GEN_B : gh::GEN_C,
                           checked_index(row, 1ull << 32, "row"),
                           checked_index(col, 1ull << 32, "column"));
+}
+
+// -- narrow GEMM check bindings (Burn-in, part 6: gpuhealth_gemm_narrow.hip) --
+static int parse_narrow_dtype(const std::string& dtype) {
+  const int dt = parse_dtype(dtype);
+  if (dt != gh::FP8 && dt != gh::MXFP4)
+    throw py::value_error("the narrow GEMM check runs fp8 and mxfp4 only");
+  return dt;
+}
+
+// (matrix "a", "b", "sa" or "sb", row, col, xor mask); the kind, the place and
+// the width of the mask are checked against dtype and shape by
+// run_gemm_narrow_exact
+typedef std::optional<std::tuple<std::string, int64_t, int64_t, int64_t>> inject_narrow_t;
+
+static std::optional<ghgemm::NarrowInject> checked_narrow_inject(const inject_narrow_t& in) {
+  if (!in) return std::nullopt;
+  const auto& [matrix, row, col, mask] = *in;
+  ghgemm::NarrowInject inj;
+  if (matrix == "a") inj.which = ghgemm::NARROW_A;
+  else if (matrix == "b") inj.which = ghgemm::NARROW_B;
+  else if (matrix == "sa") inj.which = ghgemm::NARROW_SA;
+  else if (matrix == "sb") inj.which = ghgemm::NARROW_SB;
+  else throw py::value_error("injected matrix must be a, b, sa or sb (got '" + matrix + "')");
+  inj.row = checked_index(row, 1ull << 32, "injected row");
+  inj.col = checked_index(col, 1ull << 32, "injected column");
+  inj.mask = checked_index(mask, 1ull << 32, "xor mask");
+  return inj;
+}
+
+static py::dict gemm_narrow_exact(int device, const std::string& dtype, int64_t m, int64_t n,
+                                  int64_t k, uint32_t seed, inject_narrow_t inject) {
+  const int dt = parse_narrow_dtype(dtype);
+  const std::optional<ghgemm::NarrowInject> inj = checked_narrow_inject(inject);
+  use_device(device);
+  return gemm_exact_dict(ghgemm::run_gemm_narrow_exact(dt, m, n, k, seed, inj ? &*inj : nullptr));
+}
+
+// test hook: the raw A, B, C, D and for mxfp4 SA and SB of the same fill,
+// inject and GEMM
+static py::dict debug_gemm_narrow_dump(int device, const std::string& dtype, int64_t m, int64_t n,
+                                       int64_t k, uint32_t seed, inject_narrow_t inject) {
+  const int dt = parse_narrow_dtype(dtype);
+  const std::optional<ghgemm::NarrowInject> inj = checked_narrow_inject(inject);
+  // bounded by bytes, as debug_gemm_dump; shapes the check refuses are left to it
+  const int64_t side = 65536;
+  if (m > 0 && n > 0 && k > 0 && m <= side && n <= side && k <= side &&
+      2 * ((uint64_t)m * k + (uint64_t)k * n) + 8 * (uint64_t)m * n > kGemmDumpMaxBytes)
+    throw py::value_error("the dump takes at most 192 MiB of A, B, C and D together");
+  use_device(device);
+  ghgemm::NarrowDump dump;
+  (void)ghgemm::run_gemm_narrow_exact(dt, m, n, k, seed, inj ? &*inj : nullptr, &dump);
+  py::dict d;
+  d["a"] = py::bytes(dump.a);
+  d["b"] = py::bytes(dump.b);
+  d["c"] = py::bytes(dump.c);
+  d["d"] = py::bytes(dump.d);
+  if (dt == gh::MXFP4) {
+    d["sa"] = py::bytes(dump.sa);
+    d["sb"] = py::bytes(dump.sb);
+  }
+  return d;
+}
+
+// the generator's value: the integer for fp8 a / b and every c, the e2m1 code
+// for mxfp4 a / b, the E8M0 byte for sa / sb
+static int gemm_narrow_operand(const std::string& dtype, const std::string& which, int64_t row,
+                               int64_t col, uint32_t seed) {
+  const int dt = parse_narrow_dtype(dtype);
+  uint32_t gen;
+  if (which == "a") gen = gh::GEN_A;
+  else if (which == "b") gen = gh::GEN_B;
+  else if (which == "c") gen = gh::GEN_C;
+  else if (which == "sa" && dt == gh::MXFP4) gen = gh::GEN_SA;
+  else if (which == "sb" && dt == gh::MXFP4) gen = gh::GEN_SB;
+  else throw py::value_error("which must be a, b or c, or for mxfp4 sa or sb (got '" + which + "')");
+  return gh::gen_narrow(seed, dt, gen, checked_index(row, 1ull << 32, "row"),
+                        checked_index(col, 1ull << 32, "column"));
 }
 
 static py::dict burn_in(int device, double hbm_fraction, double hbm_floor_gb_s,
@@ -2535,9 +2632,26 @@ PYBIND11_MODULE(gpuhealth, m) {
         py::arg("m") = 64, py::arg("n") = 64, py::arg("k") = 64,
         py::arg("seed") = gh::kDefaultSeed, py::arg("inject") = py::none(),
         py::arg("lds_inject") = py::none());
-  m.def("debug_lds_tr_dump", &debug_lds_tr_dump, py::arg("device") = 0);
+  m.def("debug_lds_tr_dump", &debug_lds_tr_dump, py::arg("device") = 0, py::arg("bits") = 16);
   m.def("gemm_operand", &gemm_operand, py::arg("dtype"), py::arg("which"), py::arg("row"),
         py::arg("col"), py::arg("seed") = gh::kDefaultSeed);
+  {
+    py::dict stage_k, max_k;
+    for (int dt : {(int)gh::FP8, (int)gh::MXFP4}) {
+      stage_k[kDtypeNames[dt]] = gh::narrow_stage_k(dt);
+      max_k[kDtypeNames[dt]] = gh::narrow_max_k(dt);
+    }
+    m.attr("GEMM_NARROW_STAGE_K") = stage_k;
+    m.attr("GEMM_NARROW_MAX_K") = max_k;
+  }
+  m.def("gemm_narrow_exact", &gemm_narrow_exact, py::arg("device") = 0, py::arg("dtype") = "fp8",
+        py::arg("m") = 0, py::arg("n") = 0, py::arg("k") = 0,
+        py::arg("seed") = gh::kDefaultSeed, py::arg("inject") = py::none());
+  m.def("debug_gemm_narrow_dump", &debug_gemm_narrow_dump, py::arg("device") = 0,
+        py::arg("dtype") = "fp8", py::arg("m") = 64, py::arg("n") = 64, py::arg("k") = 256,
+        py::arg("seed") = gh::kDefaultSeed, py::arg("inject") = py::none());
+  m.def("gemm_narrow_operand", &gemm_narrow_operand, py::arg("dtype"), py::arg("which"),
+        py::arg("row"), py::arg("col"), py::arg("seed") = gh::kDefaultSeed);
   m.def("flop_per_mfma", [](const std::string& dtype) {
     return gh::flop_per_mfma(parse_dtype(dtype)); }, py::arg("dtype"));
   m.def("decode_location", &decode_location_py, py::arg("xcc_id_reg"), py::arg("hw_id_reg"));

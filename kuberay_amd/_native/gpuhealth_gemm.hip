@@ -19,64 +19,21 @@
 #include <vector>
 
 #include "gpuhealth_gemm.hpp"
+#include "gpuhealth_gemm_device.hpp"
 #include "gpuhealth_ref.hpp"
 
 #if defined(__HIP_DEVICE_COMPILE__) && !defined(__gfx950__)
 #error "gpuhealth targets gfx950 (MI355X) only"
 #endif
 
-#define HIP_CHECK(expr)                                                        \
-  do {                                                                         \
-    hipError_t _e = (expr);                                                    \
-    if (_e != hipSuccess) {                                                    \
-      throw std::runtime_error(std::string("HIP error: ") +                    \
-                               hipGetErrorString(_e) + " at " #expr);          \
-    }                                                                          \
-  } while (0)
-
 namespace ghgemm {
 namespace {
-
-// Frees every device allocation and event it was handed, on every path out.
-struct DeviceScope {
-  std::vector<void*> ptrs;
-  std::vector<hipEvent_t> events;
-  ~DeviceScope() {
-    for (hipEvent_t e : events) (void)hipEventDestroy(e);
-    for (void* p : ptrs) (void)hipFree(p);
-  }
-  void* alloc(size_t bytes) {
-    void* p = nullptr;
-    HIP_CHECK(hipMalloc(&p, bytes));
-    ptrs.push_back(p);
-    return p;
-  }
-  hipEvent_t event() {
-    hipEvent_t e;
-    HIP_CHECK(hipEventCreate(&e));
-    events.push_back(e);
-    return e;
-  }
-};
-
-constexpr unsigned long long kNoBadWord = ~0ull;
 
 // the operand and accumulator registers of mfma_f32_16x16x32, as in gpuhealth.hip
 typedef __attribute__((ext_vector_type(8))) __bf16 frag_ab_t;
 typedef __attribute__((ext_vector_type(8))) _Float16 frag_f16_t;
 typedef __attribute__((ext_vector_type(4))) float frag_cd_t;
 typedef __attribute__((ext_vector_type(4))) uint32_t frag_u32x4_t;
-
-__device__ inline uint32_t read_xcc_id_reg() {
-  uint32_t v;
-  asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(v));
-  return v;
-}
-__device__ inline uint32_t read_hw_id_reg() {
-  uint32_t v;
-  asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(v));
-  return v;
-}
 
 // ---------------------------------------------------------------------------
 // Burn-in, part 5: GEMM check — D = A·B + C on matrices in device memory,
@@ -85,8 +42,8 @@ __device__ inline uint32_t read_hw_id_reg() {
 //
 // A is M x K and B is K x N, both row-major 16-bit (bf16 or f16); C and D are
 // fp32 M x N. M, N and K are multiples of 64, so there are no edge tiles. fp8
-// and MXFP4 would need the ..._tr_b8 / ..._tr_b4 reads and scale staging and
-// are not done here.
+// and MXFP4, with the ..._tr_b8 / ..._tr_b4 reads and the MX scales, are the
+// narrow check of gpuhealth_gemm_narrow.hip.
 //
 // A workgroup of four waves owns a 64 x 64 tile of D, a wave a 32 x 32
 // quadrant of it: 2 x 2 tiles of mfma_f32_16x16x32, four accumulators that
@@ -129,9 +86,6 @@ __device__ inline uint32_t read_hw_id_reg() {
 // 0 of wave 0 stores the location key of where the workgroup ran. No workgroup
 // waits on another.
 // ---------------------------------------------------------------------------
-#define GH_LDS __attribute__((address_space(3)))
-#define GH_GLOBAL __attribute__((address_space(1)))
-
 typedef __attribute__((ext_vector_type(4))) short frag_i16x4_t;
 typedef __attribute__((ext_vector_type(8))) short frag_i16x8_t;
 
@@ -331,12 +285,6 @@ __global__ void gemm_check_kernel(const float* __restrict__ d, int dtype, uint32
   atomicAdd(&stats[tile].mismatches, (unsigned long long)__popcll(bad));
   atomicMin(&stats[tile].first_bad,
             (unsigned long long)row * n + col0 + (unsigned long long)(__ffsll(bad) - 1));
-}
-
-static std::string device_bytes(const void* ptr, size_t bytes) {
-  std::string host(bytes, '\0');
-  HIP_CHECK(hipMemcpy(&host[0], ptr, bytes, hipMemcpyDeviceToHost));
-  return host;
 }
 
 }  // namespace

@@ -71,4 +71,35 @@ Result run_gemm_exact(int dtype, int64_t m, int64_t n, int64_t k, uint32_t seed,
 // one wave's transposed LDS read of words that hold their own index: 64 x 4
 std::vector<std::vector<int>> run_debug_lds_tr_dump();
 
+// --- the narrow check: fp8 and mxfp4 (gpuhealth_gemm_narrow.hip) -----------
+
+enum NarrowMatrix : int { NARROW_A = 0, NARROW_B = 1, NARROW_SA = 2, NARROW_SB = 3 };
+
+// Test hook: an xor into one element of A or B (8 bits for fp8, the 4 bits of
+// an e2m1 code for mxfp4) or into one scale byte of SA or SB (mxfp4 only) in
+// device memory, between the fill and the GEMM. row and col count elements,
+// for the scales blocks of 32 along K.
+struct NarrowInject {
+  int which = NARROW_A;
+  uint32_t row = 0, col = 0, mask = 0;
+};
+
+struct NarrowDump {
+  std::string a, b, c, d, sa, sb;  // sa and sb stay empty for fp8
+};
+
+// As run_gemm_exact, for gh::FP8 and gh::MXFP4. m and n are multiples of 64 up
+// to gh::kGemmMaxMN, k a multiple of gh::narrow_stage_k(dtype) up to
+// gh::narrow_max_k(dtype); 0 takes the same defaults. Throws
+// std::invalid_argument for anything else, for another data type, and for an
+// inject outside its matrix, with a mask wider than its element or of a scale
+// with fp8.
+Result run_gemm_narrow_exact(int dtype, int64_t m, int64_t n, int64_t k, uint32_t seed,
+                             const NarrowInject* inject = nullptr, NarrowDump* dump = nullptr);
+
+// One wave's ds_read_b64_tr_b8 (bits = 8, 64 x 8) or ds_read_b64_tr_b4 (bits =
+// 4, 64 x 16) of 512 bytes in which lane l points at byte 8 l: for every lane
+// and output element the source, as lane * elements-per-lane + element.
+std::vector<std::vector<int>> run_debug_lds_tr_dump_narrow(int bits);
+
 }  // namespace ghgemm

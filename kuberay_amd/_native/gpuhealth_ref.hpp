@@ -428,4 +428,181 @@ GH_HD inline uint16_t gemm_encode(int dtype, int value) {
   return dtype == F16 ? f32_to_f16((float)value) : f32_to_bf16((float)value);
 }
 
+// ---------------------------------------------------------------------------
+// Narrow GEMM check: the same D = A·B + C for fp8 (OCP e4m3) and MXFP4
+//
+// Layouts, all row-major: A is M x K and B is K x N; fp8 is a byte per
+// element, mxfp4 two e2m1 codes per byte along the row (along K for A, along N
+// for B), the even element in the low nibble as pack_fp4 has it. The MX scales
+// are bytes, SA[M][K / 32] and SB[K / 32][N]; block kb covers k = 32 kb .. + 31.
+// C and D are fp32. The generator is the matrix hash above (full 32-bit row
+// and column); gemm_matrix_hash takes GEN_SA and GEN_SB as well.
+//
+// Exactness premise. fp8: A, B and C are integers in [-8, 8] (e4m3 holds them
+// exactly, bit 0 of every operand stays 0), so |D| <= 64 K + 8 < 2^24 for
+// K <= 65536, as for bf16. mxfp4: A and B take all 16 e2m1 codes, at most 12
+// half units, and the scales are 126, 127 or 128 (x0.5, x1, x2); in units of
+// 1/16 one product is at most 12 · 12 · 2^4 = 2304 and C adds at most 128, so
+// 2304 K + 128 < 2^24 holds up to K = 7168 and K is capped at 4096. Every
+// partial sum is then a multiple of 1/16 below 2^20 and every accumulation
+// order gives the same fp32 value. That the scaled MFMA keeps sums of this
+// size exact is shown on the device for the hashed data at K = 4096 (and for
+// fp8 at K = 65536) by tests/test_gpu_gemm_narrow.py; for other data of the
+// same range it is argued from the bound and not shown. The data never holds
+// a subnormal or a non-finite fp8 operand.
+// ---------------------------------------------------------------------------
+constexpr uint32_t kNarrowMaxKFp8 = 65536;   // 64 K + 8 < 2^24
+constexpr uint32_t kNarrowMaxKMxfp4 = 4096;  // 2304 K + 128 < 2^24 up to 7168
+constexpr uint32_t kNarrowMaxProductX16 = 12 * 12 * 16;  // mxfp4, in sixteenths
+
+GH_HD constexpr uint32_t narrow_stage_k(int dtype) { return dtype == MXFP4 ? 256u : 128u; }
+GH_HD constexpr uint32_t narrow_max_k(int dtype) {
+  return dtype == MXFP4 ? kNarrowMaxKMxfp4 : kNarrowMaxKFp8;
+}
+// elements of A or B that one byte holds
+GH_HD constexpr uint32_t narrow_per_byte(int dtype) { return dtype == MXFP4 ? 2u : 1u; }
+
+// e2m1 code 0..15 of an mxfp4 A[row][col] or B[row][col]
+GH_HD inline uint32_t gemm_fp4_of(uint32_t matrix_hash, uint32_t row, uint32_t col) {
+  return (mix32(mix32(matrix_hash ^ row) + col) >> 8) & 15u;
+}
+// E8M0 byte of SA[row][block] or SB[block][col]: 126, 127 or 128
+GH_HD inline uint32_t gemm_scale_of(uint32_t matrix_hash, uint32_t row, uint32_t col) {
+  return 126u + (mix32(mix32(matrix_hash ^ row) + col) >> 8) % 3u;
+}
+
+// What the generator puts at [row][col] of a matrix of the narrow check: the
+// integer for fp8 A and B and for every C, the e2m1 code for mxfp4 A and B, the
+// E8M0 byte for SA and SB.
+GH_HD inline int gen_narrow(uint32_t seed, int dtype, uint32_t which, uint32_t row, uint32_t col) {
+  const uint32_t h = gemm_matrix_hash(seed, dtype, which);
+  if (which == GEN_SA || which == GEN_SB) return (int)gemm_scale_of(h, row, col);
+  if (dtype == MXFP4 && which != GEN_C) return (int)gemm_fp4_of(h, row, col);
+  return gemm_int_of(h, row, col);
+}
+
+// the byte of A or B that holds elements [row][col ..] (col a multiple of
+// narrow_per_byte), as it lies in memory
+GH_HD inline uint8_t narrow_operand_byte(uint32_t matrix_hash, int dtype, uint32_t row,
+                                         uint32_t col) {
+  if (dtype == MXFP4)
+    return pack_fp4(gemm_fp4_of(matrix_hash, row, col), gemm_fp4_of(matrix_hash, row, col + 1));
+  return f32_to_e4m3((float)gemm_int_of(matrix_hash, row, col));
+}
+
+// D[row][col] of the K-deep product in units of 1/16, in integer arithmetic only
+GH_HD inline int64_t gemm_narrow_reference_x16(uint32_t seed, int dtype, uint32_t K, uint32_t row,
+                                               uint32_t col) {
+  if (dtype != MXFP4) return 16 * (int64_t)gemm_reference_element(seed, dtype, K, row, col);
+  const uint32_t ha = mix32(gemm_matrix_hash(seed, dtype, GEN_A) ^ row);  // the row hoisted
+  const uint32_t hsa = mix32(gemm_matrix_hash(seed, dtype, GEN_SA) ^ row);
+  const uint32_t hb = gemm_matrix_hash(seed, dtype, GEN_B);
+  const uint32_t hsb = gemm_matrix_hash(seed, dtype, GEN_SB);
+  int64_t acc = 16 * (int64_t)gen_narrow(seed, dtype, GEN_C, row, col);
+  for (uint32_t kb = 0; kb < K / 32u; ++kb) {
+    // (a/2 · 2^(sa-127)) · (b/2 · 2^(sb-127)) · 16 = a·b · 2^(sa+sb-252)
+    const int shift = (int)(126u + (mix32(hsa + kb) >> 8) % 3u) +
+                      (int)gemm_scale_of(hsb, kb, col) - 252;
+    int32_t part = 0;
+    for (uint32_t k = 32u * kb; k < 32u * kb + 32u; ++k)
+      part += e2m1_half_units((mix32(ha + k) >> 8) & 15u) *
+              e2m1_half_units(gemm_fp4_of(hb, k, col));
+    acc += (int64_t)part * ((int64_t)1 << shift);
+  }
+  return acc;
+}
+GH_HD inline float gemm_narrow_reference(uint32_t seed, int dtype, uint32_t K, uint32_t row,
+                                         uint32_t col) {
+  // |x16| < 2^24, so the conversion and the division by 16 are both exact
+  return (float)gemm_narrow_reference_x16(seed, dtype, K, row, col) * 0.0625f;
+}
+
+// ---------------------------------------------------------------------------
+// Narrow GEMM check: where a stage lies in LDS, shared by the kernel and by
+// tests/native/gemm_narrow_ref_check.cpp, which shows every address in bounds
+// and the placement complete before the kernel runs at all.
+//
+// A stage is 8 KiB of A and 8 KiB of B of one 64 x 64 tile of D, 512 slots of
+// 16 bytes per operand. A: 64 rows of 128 bytes for both types (128 fp8 or 256
+// e2m1 of K), eight chunks per row. B: fp8 128 k-rows of 64 bytes, four chunks
+// per row; mxfp4 256 k-rows of 32 bytes, two chunks per row. Slot s of an
+// operand holds chunk (s % per_row) ^ swizzle(row) of row s / per_row.
+//
+// Swizzles (correctness does not depend on them):
+//   A: (row >> 1) & 7, as in the 16-bit check: the 16 rows that 16 lanes read
+//      at one chunk fall into 16 different places of the 64 banks.
+//   B fp8: (row >> 2) & 3. A transposed read of 16 lanes touches 8 consecutive
+//      k-rows at one chunk and the four lane groups 32 of them; rows 64 bytes
+//      apart repeat their banks every 4 rows, the xor moves rows 4 .. 15 of
+//      every 16 onto the other three chunks, so 16 rows cover the 64 banks once.
+//   B mxfp4: (row >> 3) & 1. A transposed read of 16 lanes touches 16
+//      consecutive k-rows, 8 bytes each; rows 32 bytes apart repeat every 8
+//      rows and there is one bit of chunk to give: rows 8 .. 15 go to the other
+//      chunk. The four lane groups are 32 rows apart and still share banks.
+// ---------------------------------------------------------------------------
+constexpr uint32_t kNarrowOperandBytes = 8192;
+constexpr uint32_t kNarrowSlots = kNarrowOperandBytes / 16;
+
+struct NarrowChunk {
+  uint32_t row, byte;  // row of the tile (of M for A, of the stage's K for B), byte within it
+};
+
+GH_HD constexpr uint32_t narrow_b_row_bytes(int dtype) { return dtype == MXFP4 ? 32u : 64u; }
+GH_HD inline uint32_t narrow_a_swizzle(uint32_t row) { return (row >> 1) & 7u; }
+GH_HD inline uint32_t narrow_b_swizzle(int dtype, uint32_t row) {
+  return dtype == MXFP4 ? (row >> 3) & 1u : (row >> 2) & 3u;
+}
+
+// what belongs into 16-byte slot `slot` (0..511) of A's and of B's part of a stage
+GH_HD inline NarrowChunk narrow_a_source(uint32_t slot) {
+  const uint32_t row = slot >> 3;
+  return {row, 16u * ((slot & 7u) ^ narrow_a_swizzle(row))};
+}
+GH_HD inline NarrowChunk narrow_b_source(int dtype, uint32_t slot) {
+  const uint32_t per_row = narrow_b_row_bytes(dtype) / 16u, row = slot / per_row;
+  return {row, 16u * ((slot % per_row) ^ narrow_b_swizzle(dtype, row))};
+}
+
+// Byte offset within A's 8 KiB of the A fragment of lane (i, g) for tile row
+// `row` at MFMA step t of the stage. fp8: 8 bytes, k = 32 t + 8 g + j. mxfp4:
+// 16 bytes, k = 128 t + 32 g + j, two to a byte.
+GH_HD inline uint32_t narrow_a_read(int dtype, uint32_t row, uint32_t t, uint32_t g) {
+  const uint32_t byte = dtype == MXFP4 ? 64u * t + 16u * g : 32u * t + 8u * g;
+  return row * 128u + 16u * ((byte >> 4) ^ narrow_a_swizzle(row)) + (byte & 15u);
+}
+
+// Lane maps of the two transposed reads, as debug_lds_tr_dump(bits=8 / 4)
+// measures them (tests/test_gpu_gemm_narrow.py); both stay within a group of 16
+// lanes, b = l & ~15, i = l & 15. Lane l hands in the address of 8 bytes.
+//   ds_read_b64_tr_b8: byte e (0..7) of lane l's result is byte i % 8 of what
+//     lane b + 2 e + i / 8 pointed at. Read as a matrix whose row e is the 16
+//     bytes of lanes b + 2 e and b + 2 e + 1, lane l receives column i.
+//   ds_read_b64_tr_b4: nibble e (0..15) of lane l's result is nibble i of what
+//     lane b + e pointed at: row e is the 16 nibbles of lane b + e, lane l
+//     receives column i.
+// The value is the source as lane * elements-per-lane + element.
+GH_HD inline uint32_t narrow_tr8_source(uint32_t lane, uint32_t e) {
+  const uint32_t b = lane & ~15u, i = lane & 15u;
+  return 8u * (b + 2u * e + i / 8u) + i % 8u;
+}
+GH_HD inline uint32_t narrow_tr4_source(uint32_t lane, uint32_t e) {
+  return 16u * ((lane & ~15u) + e) + (lane & 15u);
+}
+
+// Byte offset within B's 8 KiB that lane (i, g) hands to the transposed read
+// for the 16 columns from tile column `col` (a multiple of 16) at MFMA step t.
+// fp8: one ds_read_b64_tr_b8; the lane points at k-row 32 t + 8 g + i / 2,
+// bytes col + 8 (i % 2) .. + 7, and receives B[32 t + 8 g + e][col + i].
+// mxfp4: two ds_read_b64_tr_b4, half h; the lane points at k-row 128 t + 32 g +
+// 16 h + i, the 16 nibbles from column col, and receives in nibble e
+// B[128 t + 32 g + 16 h + e][col + i]. k runs along the register, as MFMA wants.
+GH_HD inline uint32_t narrow_b_read(int dtype, uint32_t col, uint32_t t, uint32_t g, uint32_t h,
+                                    uint32_t i) {
+  const uint32_t row = dtype == MXFP4 ? 128u * t + 32u * g + 16u * h + i
+                                      : 32u * t + 8u * g + i / 2u;
+  const uint32_t byte = dtype == MXFP4 ? col / 2u : col + 8u * (i % 2u);
+  return row * narrow_b_row_bytes(dtype) +
+         16u * ((byte >> 4) ^ narrow_b_swizzle(dtype, row)) + (byte & 15u);
+}
+
 }  // namespace gh

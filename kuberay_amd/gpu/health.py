@@ -66,6 +66,9 @@ class HealthReport:
     # GEMM check of the burn-in level; None unless it was asked for
     gemm_exact: Optional[Dict[str, bool]] = None
     gemm_faulty: Optional[List[str]] = None
+    # narrow GEMM check (fp8, mxfp4) of the burn-in level; None unless asked for
+    gemm_narrow_exact: Optional[Dict[str, bool]] = None
+    gemm_narrow_faulty: Optional[List[str]] = None
 
 
 def _rocm_smi_ok() -> bool:
@@ -185,14 +188,19 @@ def _mfma_load(native, device: int, load_seconds: float, floors: Dict[str, float
 GEMM_DTYPES = ("bf16", "f16")
 
 
-def _gemm_exact(native, device: int):
-    """The GEMM check at its default shape, once per 16-bit data type. Returns
-    (ok by data type, faulty, problems)."""
-    if not hasattr(native, "gemm_exact"):
-        return {}, [], ["gemm: asked for, but this native module has no gemm_exact"]
+GEMM_NARROW_DTYPES = ("fp8", "mxfp4")
+
+
+def _gemm_exact(native, device: int, entry: str = "gemm_exact", dtypes=GEMM_DTYPES):
+    """The GEMM check at its default shape, once per 16-bit data type; with
+    ``entry="gemm_narrow_exact"`` the narrow one, once per ``GEMM_NARROW_DTYPES``.
+    Returns (ok by data type, faulty, problems)."""
+    if not hasattr(native, entry):
+        what = "gemm" if entry == "gemm_exact" else "gemm narrow"
+        return {}, [], [f"{what}: asked for, but this native module has no {entry}"]
     ok, faulty, problems = {}, [], []
-    for dtype in GEMM_DTYPES:
-        r = native.gemm_exact(device, dtype)
+    for dtype in dtypes:
+        r = getattr(native, entry)(device, dtype)
         ok[dtype] = bool(r["ok"])
         if ok[dtype]:
             continue
@@ -215,7 +223,8 @@ def check_gpu_burn_in(device: int = 0,
                       require_cu_coverage: bool = False,
                       load_seconds: float = 0.0,
                       mfma_floor_tflops: Optional[Dict[str, float]] = None,
-                      gemm: bool = False) -> HealthReport:
+                      gemm: bool = False,
+                      gemm_narrow: bool = False) -> HealthReport:
     """Burn-in level: the full gate of ``check_gpu_health``, then the exact
     MFMA verification on the bf16, f16, fp8 and MXFP4 data paths, then a
     data-verifying pattern sweep over ``hbm_fraction`` of the free HBM, then
@@ -230,6 +239,9 @@ def check_gpu_burn_in(device: int = 0,
     exact f16 GEMM staged through LDS by direct-to-LDS loads and read back
     with the transposed LDS read. A wrong element is unhealthy, and ``detail``
     names the data type, the first bad element and the CU of its tile.
+    With ``gemm_narrow`` the same check for fp8 and MXFP4 follows in the GEMM
+    check's place: byte and nibble operands through the 8-bit and 4-bit
+    transposed LDS reads, MX scales from device memory; reported alike.
     Raises GpuHealthError on non-GPU hosts; ``detail`` names what failed."""
     if not gpu_node():
         raise GpuHealthError("not a GPU node (/dev/kfd missing)")
@@ -290,6 +302,15 @@ def check_gpu_burn_in(device: int = 0,
             return _hip_failure(e, rocm_ok)
         problems.extend(gemm_problems)
         healthy = healthy and not gemm_problems
+    narrow_ok = narrow_faulty = None
+    if gemm_narrow:
+        try:
+            narrow_ok, narrow_faulty, narrow_problems = _gemm_exact(
+                native, device, "gemm_narrow_exact", GEMM_NARROW_DTYPES)
+        except RuntimeError as e:
+            return _hip_failure(e, rocm_ok)
+        problems.extend(narrow_problems)
+        healthy = healthy and not narrow_problems
     load_ok = load_by_dtype = load_tflops = load_clock = load_faulty = None
     if load_seconds > 0.0:
         try:
@@ -317,6 +338,7 @@ def check_gpu_burn_in(device: int = 0,
         mfma_load_clock_mhz=load_clock, mfma_load_faulty=load_faulty,
         mfma_load_ok_by_dtype=load_by_dtype,
         gemm_exact=gemm_ok, gemm_faulty=gemm_faulty,
+        gemm_narrow_exact=narrow_ok, gemm_narrow_faulty=narrow_faulty,
     )
 
 

@@ -19,6 +19,11 @@ when it ran.
 ``amd.com/gpu-burn-in-gemm``): one exact bf16 and one exact f16 GEMM through
 direct-to-LDS loads, transposed LDS reads and MFMA, milliseconds long. Its
 fields appear in the output only when it was asked for.
+
+``--deep --gemm-narrow`` adds the narrow GEMM check (annotation
+``amd.com/gpu-burn-in-gemm-narrow``): the same for fp8 and MXFP4, through the
+8-bit and 4-bit transposed LDS reads with the MX scales from device memory.
+Its fields follow those of ``--gemm``.
 """
 from __future__ import annotations
 
@@ -57,9 +62,14 @@ def main(argv=None) -> int:
     parser.add_argument("--gemm", action="store_true",
                         help="with --deep: the exact GEMM check through "
                              "direct-to-LDS loads and transposed LDS reads")
+    parser.add_argument("--gemm-narrow", action="store_true",
+                        help="with --deep: the exact fp8 and MXFP4 GEMM check "
+                             "through the 8-bit and 4-bit transposed LDS reads")
     args = parser.parse_args(argv)
     if args.gemm and not args.deep:
         parser.error("--gemm needs --deep")
+    if args.gemm_narrow and not args.deep:
+        parser.error("--gemm-narrow needs --deep")
     if args.load_seconds and not args.deep:
         parser.error("--load-seconds needs --deep")
     if args.mfma_floor_tflops and not args.load_seconds:
@@ -83,6 +93,8 @@ def main(argv=None) -> int:
         load = {"load_seconds": args.load_seconds, "mfma_floor_tflops": floors or None}
     if args.gemm:
         load["gemm"] = True
+    if args.gemm_narrow:
+        load["gemm_narrow"] = True
 
     try:
         if args.deep:
@@ -120,6 +132,9 @@ def main(argv=None) -> int:
                            mfma_load_faulty=report.mfma_load_faulty)
             if args.gemm:
                 out.update(gemm_exact=report.gemm_exact, gemm_faulty=report.gemm_faulty)
+            if args.gemm_narrow:
+                out.update(gemm_narrow_exact=report.gemm_narrow_exact,
+                           gemm_narrow_faulty=report.gemm_narrow_faulty)
             print(json.dumps(out))
         else:
             cu = (f" cu_total={report.cu_total} cu_covered={report.cu_covered} "
@@ -131,6 +146,9 @@ def main(argv=None) -> int:
                        f"mfma_load_faulty={report.mfma_load_faulty}")
             if args.gemm:
                 cu += f" gemm_exact={report.gemm_exact} gemm_faulty={report.gemm_faulty}"
+            if args.gemm_narrow:
+                cu += (f" gemm_narrow_exact={report.gemm_narrow_exact} "
+                       f"gemm_narrow_faulty={report.gemm_narrow_faulty}")
             print(f"healthy={report.healthy} mfma_ok={report.mfma_ok} "
                   f"hbm_gb_s={report.hbm_gb_s} rocm_smi_ok={report.rocm_smi_ok} "
                   f"mfma_exact={report.mfma_exact} "

@@ -250,6 +250,8 @@ GPU_BURN_IN_LOAD_PROBE_OVERHEAD_SECONDS = 20
 # amd.com/gpu-burn-in: "true" adds the GEMM check to the burn-in (``--gemm``).
 # The check is milliseconds long, so the startup probe's timeout stays.
 GPU_BURN_IN_GEMM_ANNOTATION_KEY = "amd.com/gpu-burn-in-gemm"
+# The same for the narrow GEMM check, fp8 and MXFP4 (``--gemm-narrow``).
+GPU_BURN_IN_GEMM_NARROW_ANNOTATION_KEY = "amd.com/gpu-burn-in-gemm-narrow"
 
 # Device nodes every ROCm container needs (AMD k8s device plugin mounts these
 # automatically when amd.com/gpu is requested; we also support explicit

@@ -1,0 +1,25 @@
+"""tests/native/gemm_narrow_ref_check.cpp, a stand-alone g++ program over
+gpuhealth_ref.hpp: the narrow GEMM check's generators, bounds and reference, and
+its stage placement and LDS read addresses composed with the tr lane maps."""
+import os
+import shutil
+import subprocess
+from pathlib import Path
+
+import pytest
+
+ROOT = Path(__file__).resolve().parent.parent
+CXX = os.environ.get("CXX", "g++")
+
+
+def test_gemm_narrow_ref_check(tmp_path):
+    if shutil.which(CXX) is None:
+        pytest.skip(f"{CXX} not available")
+    exe = tmp_path / "gemm_narrow_ref_check"
+    build = subprocess.run(
+        [CXX, "-std=c++17", "-Wall", "-Wextra", "-O2", f"-I{ROOT / 'kuberay_amd' / '_native'}",
+         str(ROOT / "tests" / "native" / "gemm_narrow_ref_check.cpp"), "-o", str(exe)],
+        capture_output=True, text=True)
+    assert build.returncode == 0, build.stderr
+    run = subprocess.run([str(exe)], capture_output=True, text=True, timeout=300)
+    assert run.returncode == 0 and "gemm_narrow_ref_check OK" in run.stdout, run.stdout + run.stderr
