@@ -3,8 +3,8 @@ live next to the sources so it travels to GPU boxes with the repo snapshot).
 
 Extensions:
   * gpuhealth  — HIP/gfx950 on-device health probes and burn-in
-                 (gpuhealth.hip, gpuhealth_gemm.hip and gpuhealth_gemm_narrow.hip
-                 over gpuhealth_ref.hpp)
+                 (gpuhealth.hip, gpuhealth_gemm.hip, gpuhealth_gemm_narrow.hip
+                 and gpuhealth_attn.hip over gpuhealth_ref.hpp)
   * engine     — C++ control-plane core: object cache + indices + native
                  JSON encoding and decoding and model-tree copies (engine.cpp
                  bindings over store_core.hpp, json_decode.hpp and
@@ -45,7 +45,8 @@ def _needs_rebuild(src: Path, out: Path, *deps: Path) -> bool:
 
 def build_gpuhealth(force: bool = False) -> Path:
     src = HERE / "gpuhealth.hip"
-    gemm_srcs = [HERE / "gpuhealth_gemm.hip", HERE / "gpuhealth_gemm_narrow.hip"]
+    gemm_srcs = [HERE / "gpuhealth_gemm.hip", HERE / "gpuhealth_gemm_narrow.hip",
+                 HERE / "gpuhealth_attn.hip"]
     out = HERE / f"gpuhealth{_ext_suffix()}"
     if not force and not _needs_rebuild(src, out, *gemm_srcs, HERE / "gpuhealth_ref.hpp",
                                         HERE / "gpuhealth_gemm.hpp",
@@ -53,7 +54,7 @@ def build_gpuhealth(force: bool = False) -> Path:
         return out
     common = [HIPCC, f"--offload-arch={GFX_ARCH}", "-O3", "-std=c++17", "-fPIC"]
     with tempfile.TemporaryDirectory() as tmp:
-        # The GEMM checks' kernels are translation units of their own, built
+        # The GEMM and attention checks' kernels are translation units of their own, built
         # with packed fp32 arithmetic (v_pk_*_f32) disabled for the device code
         # (the reason is at the top of gpuhealth_gemm.hip); the host pass of
         # those compiles does not know the feature and says so in a warning.

@@ -187,12 +187,48 @@
 //                    gemm_narrow_exact(inject=) into A, B, SA or SB in device
 //                    memory, debug_gemm_narrow_dump, gemm_narrow_operand.
 //                    Details: gpuhealth_gemm_narrow.hip.
+//   * attn_exact   — opt-in, single-shot, an entry point of its own: what an
+//                    attention kernel does between its two matrix products,
+//                    which no check above executes. Unnormalised single-head
+//                    attention forward with online softmax for bf16 / f16:
+//                    Q [M, 64], K and V [N, 64] in device memory, fp32
+//                    O~ = Σ_j 2^(s - m) V[j], m = max_j s and l = Σ_j 2^(s - m)
+//                    with s = Q·Kᵀ, the form a flash-decoding split writes.
+//                    Four waves own 64 queries and walk K and V in blocks of
+//                    64 keys staged as in gemm_exact; Sᵀ = K·Qᵀ by MFMA, then
+//                    fp32 max / subtract / multiply / add on the accumulators,
+//                    v_exp_f32, v_permlane16_swap / v_permlane32_swap across
+//                    the lane groups, v_cvt_pk_bf16_f32 / v_cvt_pk_f16_f32,
+//                    and the converted accumulators are the B operand of the
+//                    second MFMA without leaving the register file; Vᵀ comes
+//                    out of LDS through ds_read_b64_tr_b16 in P's register
+//                    order. Q holds integers in [-2, 2], K is two-hot ±1 and V
+//                    integers in [-8, 8], so every exponent is an integer in
+//                    [-8, 0] and every sum a multiple of 2^-8 below 2^15 for
+//                    N <= 4096 (the host refuses a larger N, M above 65536 and
+//                    anything that is no multiple of 64 with ValueError): O~,
+//                    m and l are compared with == against integer arithmetic
+//                    from the generators, and a bad block of 64 queries is
+//                    named by the XCC/SE/SH/CU its workgroup ran on. Default
+//                    shape: N = 1024 and M = 64 x 2 x the number of CUs.
+//                    Measured (debug_permlane_dump, debug_exp2_dump,
+//                    tests/test_gpu_attn_exact.py): the lane maps of the two
+//                    swaps, and v_exp_f32 exact on every integer from 0 to
+//                    -126 and 0 for -inf, so production uses the exp unit.
+//                    Cannot show: v_exp_f32 only ever sees integers, so its
+//                    fraction path is not covered; there is no final division,
+//                    no mask and no head dimension but 64; the operands' low
+//                    mantissa bits are still never set. Test hooks:
+//                    attn_exact(inject=) into Q, K or V in device memory,
+//                    debug_attn_dump, attn_operand. Details:
+//                    gpuhealth_attn.hip.
 //
 // What must agree between host and device (pattern, generators, encoders,
 // reference) is in gpuhealth_ref.hpp. The kernels of gemm_exact ("Burn-in,
 // part 5") and their host code are in gpuhealth_gemm.hip, those of
-// gemm_narrow_exact ("part 6") in gpuhealth_gemm_narrow.hip, translation units
-// of their own (the reason is at the top of the first); this file binds them.
+// gemm_narrow_exact ("part 6") in gpuhealth_gemm_narrow.hip and those of
+// attn_exact ("part 7") in gpuhealth_attn.hip, translation units of their own
+// (the reason is at the top of the first); this file binds them.
 //
 // Build: hipcc --offload-arch=gfx950 (see kuberay_amd/_native/build.py).
 // Wavefront width is 64 on CDNA4 — all wave math below hard-codes 64.
@@ -2543,6 +2579,113 @@ static int gemm_narrow_operand(const std::string& dtype, const std::string& whic
                         checked_index(col, 1ull << 32, "column"));
 }
 
+// -- attention check bindings (Burn-in, part 7: gpuhealth_attn.hip) ----------
+static int parse_attn_dtype(const std::string& dtype) {
+  const int dt = parse_dtype(dtype);
+  if (dt != gh::BF16 && dt != gh::F16)
+    throw py::value_error("the attention check runs bf16 and f16 only");
+  return dt;
+}
+
+// (matrix "q", "k" or "v", row, col, 16-bit xor mask); the place is checked
+// against the shape by run_attn_exact
+typedef std::optional<std::tuple<std::string, int64_t, int64_t, int64_t>> inject_attn_t;
+
+static std::optional<ghgemm::AttnInject> checked_attn_inject(const inject_attn_t& in) {
+  if (!in) return std::nullopt;
+  const auto& [matrix, row, col, mask] = *in;
+  ghgemm::AttnInject inj;
+  if (matrix == "q") inj.which = ghgemm::ATTN_Q;
+  else if (matrix == "k") inj.which = ghgemm::ATTN_K;
+  else if (matrix == "v") inj.which = ghgemm::ATTN_V;
+  else throw py::value_error("injected matrix must be q, k or v (got '" + matrix + "')");
+  inj.row = checked_index(row, 1ull << 32, "injected row");
+  inj.col = checked_index(col, 1ull << 32, "injected column");
+  inj.mask = checked_index(mask, 1ull << 32, "xor mask");
+  return inj;
+}
+
+// the dict of gemm_exact with head_dim in the place of k; first_bad is (row,
+// col, got, expected) with col 0..63 in O~, 64 for m and 65 for l
+static py::dict attn_exact_dict(const ghgemm::Result& r) {
+  py::dict d;
+  py::list faulty;
+  for (const ghgemm::FaultyTile& f : r.faulty) {
+    py::dict t = location_dict(f.key);
+    t["tile"] = py::make_tuple(f.tile_row, f.tile_col);
+    t["mismatches"] = f.stats.mismatches;
+    t["first_bad"] = py::make_tuple(f.stats.first_bad / gh::kAttnOutCols,
+                                    f.stats.first_bad % gh::kAttnOutCols);
+    faulty.append(t);
+  }
+  d["dtype"] = kDtypeNames[r.dtype];
+  d["m"] = r.m;
+  d["n"] = r.n;
+  d["head_dim"] = r.k;
+  d["ok"] = r.mismatches == 0;
+  d["mismatches"] = r.mismatches;
+  if (r.first_bad >= 0)
+    d["first_bad"] = py::make_tuple(r.first_bad / gh::kAttnOutCols, r.first_bad % gh::kAttnOutCols,
+                                    r.got, r.expected);
+  else
+    d["first_bad"] = py::none();
+  d["faulty"] = faulty;
+  d["workgroups"] = r.workgroups;
+  d["cu_total"] = r.cu_total;
+  d["cu_seen"] = r.cu_seen;
+  d["elapsed_ms"] = r.elapsed_ms;
+  // for information: one cold launch, both products, nothing is gated on it
+  const double flop = 4.0 * (double)r.m * (double)r.n * (double)r.k;
+  d["tflops"] = r.elapsed_ms > 0.0 ? flop / (r.elapsed_ms * 1e-3) / 1e12 : 0.0;
+  return d;
+}
+
+static py::dict attn_exact(int device, const std::string& dtype, int64_t m, int64_t n,
+                           uint32_t seed, inject_attn_t inject) {
+  const int dt = parse_attn_dtype(dtype);
+  const std::optional<ghgemm::AttnInject> inj = checked_attn_inject(inject);
+  use_device(device);
+  return attn_exact_dict(ghgemm::run_attn_exact(dt, m, n, seed, inj ? &*inj : nullptr));
+}
+
+// test hook: the raw Q, K, V, O~, m and l of the same fill, inject and launch
+static py::dict debug_attn_dump(int device, const std::string& dtype, int64_t m, int64_t n,
+                                uint32_t seed, inject_attn_t inject) {
+  const int dt = parse_attn_dtype(dtype);
+  const std::optional<ghgemm::AttnInject> inj = checked_attn_inject(inject);
+  use_device(device);
+  ghgemm::AttnDump dump;
+  (void)ghgemm::run_attn_exact(dt, m, n, seed, inj ? &*inj : nullptr, &dump);
+  py::dict d;
+  d["q"] = py::bytes(dump.q);
+  d["k"] = py::bytes(dump.k);
+  d["v"] = py::bytes(dump.v);
+  d["o"] = py::bytes(dump.o);
+  d["m"] = py::bytes(dump.m);
+  d["l"] = py::bytes(dump.l);
+  return d;
+}
+
+static int attn_operand(const std::string& dtype, const std::string& which, int64_t row,
+                        int64_t col, uint32_t seed) {
+  const int dt = parse_attn_dtype(dtype);
+  if (which != "q" && which != "k" && which != "v")
+    throw py::value_error("which must be q, k or v (got '" + which + "')");
+  return gh::gen_attn(seed, dt, which == "q" ? gh::GEN_Q : which == "k" ? gh::GEN_KEY : gh::GEN_V,
+                      checked_index(row, 1ull << 32, "row"),
+                      checked_index(col, gh::kAttnHeadDim, "column"));
+}
+
+static std::vector<std::vector<int>> debug_permlane_dump(int device) {
+  use_device(device);
+  return ghgemm::run_debug_permlane_dump();
+}
+
+static std::vector<float> debug_exp2_dump(int device) {
+  use_device(device);
+  return ghgemm::run_debug_exp2_dump();
+}
+
 static py::dict burn_in(int device, double hbm_fraction, double hbm_floor_gb_s,
                         bool require_cu_coverage) {
   py::dict result = health_check(device, hbm_floor_gb_s, false);
@@ -2652,6 +2795,19 @@ PYBIND11_MODULE(gpuhealth, m) {
         py::arg("seed") = gh::kDefaultSeed, py::arg("inject") = py::none());
   m.def("gemm_narrow_operand", &gemm_narrow_operand, py::arg("dtype"), py::arg("which"),
         py::arg("row"), py::arg("col"), py::arg("seed") = gh::kDefaultSeed);
+  m.attr("ATTN_MAX_N") = gh::kAttnMaxN;
+  m.attr("ATTN_HEAD_DIM") = gh::kAttnHeadDim;
+  m.attr("ATTN_DEFAULT_N") = ghgemm::kAttnDefaultN;
+  m.def("attn_exact", &attn_exact, py::arg("device") = 0, py::arg("dtype") = "bf16",
+        py::arg("m") = 0, py::arg("n") = 0, py::arg("seed") = gh::kDefaultSeed,
+        py::arg("inject") = py::none());
+  m.def("debug_attn_dump", &debug_attn_dump, py::arg("device") = 0, py::arg("dtype") = "bf16",
+        py::arg("m") = 64, py::arg("n") = 64, py::arg("seed") = gh::kDefaultSeed,
+        py::arg("inject") = py::none());
+  m.def("attn_operand", &attn_operand, py::arg("dtype"), py::arg("which"), py::arg("row"),
+        py::arg("col"), py::arg("seed") = gh::kDefaultSeed);
+  m.def("debug_permlane_dump", &debug_permlane_dump, py::arg("device") = 0);
+  m.def("debug_exp2_dump", &debug_exp2_dump, py::arg("device") = 0);
   m.def("flop_per_mfma", [](const std::string& dtype) {
     return gh::flop_per_mfma(parse_dtype(dtype)); }, py::arg("dtype"));
   m.def("decode_location", &decode_location_py, py::arg("xcc_id_reg"), py::arg("hw_id_reg"));

@@ -1,6 +1,7 @@
 // gpuhealth_gemm — what gpuhealth.hip (bindings) and gpuhealth_gemm.hip
-// (kernels and their host code) share of the burn-in's GEMM check: plain
-// structs and two functions, no HIP and no pybind11 types. The two files are
+// (kernels and their host code) share of the burn-in's GEMM check, and below
+// that what it shares with gpuhealth_gemm_narrow.hip and gpuhealth_attn.hip: plain
+// structs and a few functions, no HIP and no pybind11 types. The files are
 // separate translation units so that the GEMM kernels can be compiled with a
 // switch of their own (kuberay_amd/_native/build.py) while every older kernel
 // is compiled exactly as before.
@@ -101,5 +102,43 @@ Result run_gemm_narrow_exact(int dtype, int64_t m, int64_t n, int64_t k, uint32_
 // 4, 64 x 16) of 512 bytes in which lane l points at byte 8 l: for every lane
 // and output element the source, as lane * elements-per-lane + element.
 std::vector<std::vector<int>> run_debug_lds_tr_dump_narrow(int bits);
+
+// --- the attention check: bf16 and f16 (gpuhealth_attn.hip) ----------------
+
+constexpr uint32_t kAttnDefaultN = 1024;
+
+enum AttnMatrix : int { ATTN_Q = 0, ATTN_K = 1, ATTN_V = 2 };
+
+// Test hook: an xor into one 16-bit element of Q, K or V in device memory,
+// between the fill and the launch.
+struct AttnInject {
+  int which = ATTN_Q;
+  uint32_t row = 0, col = 0, mask = 0;
+};
+
+struct AttnDump {
+  std::string q, k, v, o, m, l;
+};
+
+// Unnormalised attention forward with online softmax on the current device:
+// Q is m x 64, K and V are n x 64. 0 takes the default: n = kAttnDefaultN,
+// m = 64 * kWorkgroupsPerCu * (number of CUs). In the Result, k is the head
+// dimension, a faulty tile is a block of 64 queries (tile_col = 0) and
+// first_bad is row * gh::kAttnOutCols + col, where col 0..63 is O~, 64 is m and
+// 65 is l; mismatches counts elements of all three. Throws
+// std::invalid_argument for m or n that is no positive multiple of 64, m above
+// gh::kAttnMaxM, n above gh::kAttnMaxN (exactness), a data type other than
+// bf16 / f16 and an inject outside its matrix or with a mask wider than 16
+// bits; std::runtime_error for a failing HIP call.
+Result run_attn_exact(int dtype, int64_t m, int64_t n, uint32_t seed,
+                      const AttnInject* inject = nullptr, AttnDump* dump = nullptr);
+
+// One wave's v_permlane16_swap and v_permlane32_swap of vdst = lane, vsrc =
+// 64 + lane: [0] and [1] are the new vdst and vsrc of the 16-lane swap, [2] and
+// [3] of the 32-lane swap, 64 values each.
+std::vector<std::vector<int>> run_debug_permlane_dump();
+
+// v_exp_f32 of 0, -1, .., -126 and of -inf: 128 values
+std::vector<float> run_debug_exp2_dump();
 
 }  // namespace ghgemm

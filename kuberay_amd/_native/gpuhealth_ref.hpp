@@ -4,9 +4,12 @@
 // kernels in gpuhealth.hip lives here as plain functions that compile for both
 // sides (GH_HD): the HBM sweep pattern, the operand generators of the exact
 // MFMA check, the encoders to bf16 / f16 / OCP e4m3 / e2m1 bit patterns, the
-// exact reference product, and the matrix generator and reference of the GEMM
-// check. No HIP, no pybind11 — tests/native/
-// gpuhealth_ref_check.cpp drives it as a stand-alone g++ program.
+// exact reference product, the matrix generator and reference of the GEMM
+// checks, and the generators, the premise, the integer reference and the LDS
+// address functions of the attention check. No HIP, no pybind11 — the programs
+// under tests/native/ (gpuhealth_ref_check.cpp, gemm_ref_check.cpp,
+// gemm_narrow_ref_check.cpp, attn_ref_check.cpp) drive it as stand-alone g++
+// programs.
 //
 // Exactness premise: bf16 / f16 / fp8 operands are integers in [-8, 8], so a
 // K=32 dot product plus C is an integer below 2^12; MXFP4 operands are e2m1
@@ -603,6 +606,187 @@ GH_HD inline uint32_t narrow_b_read(int dtype, uint32_t col, uint32_t t, uint32_
   const uint32_t byte = dtype == MXFP4 ? col / 2u : col + 8u * (i % 2u);
   return row * narrow_b_row_bytes(dtype) +
          16u * ((byte >> 4) ^ narrow_b_swizzle(dtype, row)) + (byte & 15u);
+}
+
+// ---------------------------------------------------------------------------
+// Attention check: unnormalised single-head attention forward, base 2, scale 1
+//
+//   s = Q·Kᵀ,  m[i] = max_j s_ij,  l[i] = Σ_j 2^(s_ij - m_i),
+//   O~[i][d] = Σ_j 2^(s_ij - m_i) · V[j][d]
+//
+// Q is M x 64, K and V are N x 64, row-major bf16 or f16; O~, m and l are fp32.
+// No mask and no final division. The generators hash (row, col, seed) through
+// gemm_matrix_hash with GEN_Q, GEN_KEY and GEN_V:
+//   Q: dense integers in [-2, 2].
+//   K: two-hot. Row j is zero but for ±1 at two distinct columns d1(j) != d2(j)
+//      (attn_key_of), so s_ij = ±Q[i][d1] ± Q[i][d2] is an integer in [-4, 4]
+//      that costs two lookups to recompute.
+//   V: dense integers in [-8, 8].
+//
+// Exactness premise. Every s is an integer in [-4, 4], so for every row
+// max_j s - min_j s <= 8 by construction. A running maximum m_run of an online
+// softmax is the maximum over the keys seen so far, so 0 <= m_run - s <= 8 for
+// every s among them and every p = 2^(s - m_run) is a power of two in
+// [2^-8, 1]: exact in fp32, in bf16 and in f16 (normal down to 2^-14). Every partial l is a sum of at most N such
+// powers: a multiple of 2^-8 and at most N. Every partial O~ is a sum of at
+// most N products p·v with |v| <= 8: a multiple of 2^-8 of magnitude at most
+// 8 N <= 2^15 for N <= kAttnMaxN = 4096, at most 15 + 8 = 23 significant bits,
+// so it is exact in fp32 in any summation order. A rescale by
+// 2^(m_old - m_new) is exact because its result is again such a sum, under the
+// new maximum. Hence the device's O~, m and l can be compared with == against
+// integer arithmetic: Σ_j 2^(8 + s - m) · v is an int32 of magnitude at most
+// 2^23, scaled by 2^-8. That the MFMA keeps sums of this size exact is shown on
+// the device for the hashed data at N = 4096 (tests/test_gpu_attn_exact.py);
+// for other data of the same range it is argued from the bound.
+//
+// What the premise costs, beyond the zero low mantissa bits of every operand:
+// v_exp_f32 only ever sees the integers -8 .. 0 and -inf.
+// ---------------------------------------------------------------------------
+constexpr uint32_t GEN_Q = 5, GEN_KEY = 6, GEN_V = 7;  // after Which, for gemm_matrix_hash
+constexpr uint32_t kAttnHeadDim = 64;
+constexpr uint32_t kAttnBlock = 64;     // queries of a workgroup, and keys of a stage
+constexpr uint32_t kAttnMaxN = 4096;    // 8 N * 2^8 <= 2^23
+constexpr uint32_t kAttnMaxM = 65536;   // not needed for exactness: bounds what one call allocates
+constexpr uint32_t kAttnOutCols = kAttnHeadDim + 2;  // a row of the result: O~, then m, then l
+
+GH_HD inline int attn_q_of(uint32_t matrix_hash, uint32_t row, uint32_t col) {
+  return (int)((mix32(mix32(matrix_hash ^ row) + col) >> 8) % 5u) - 2;
+}
+
+struct AttnKey {
+  uint32_t d1, d2;  // distinct columns
+  int s1, s2;       // +1 or -1
+};
+GH_HD inline AttnKey attn_key_of(uint32_t matrix_hash, uint32_t row) {
+  const uint32_t h = mix32(matrix_hash ^ row);
+  AttnKey k;
+  k.d1 = (h >> 8) & 63u;
+  k.d2 = (k.d1 + 1u + (h >> 14) % 63u) & 63u;  // d1 + 1 .. d1 + 63 mod 64: never d1
+  k.s1 = (h >> 24) & 1u ? -1 : 1;
+  k.s2 = (h >> 25) & 1u ? -1 : 1;
+  return k;
+}
+GH_HD inline int attn_k_of(uint32_t matrix_hash, uint32_t row, uint32_t col) {
+  const AttnKey k = attn_key_of(matrix_hash, row);
+  return col == k.d1 ? k.s1 : col == k.d2 ? k.s2 : 0;
+}
+
+// Q[row][col], K[row][col] or V[row][col] of the attention check; which is
+// GEN_Q, GEN_KEY or GEN_V
+GH_HD inline int gen_attn(uint32_t seed, int dtype, uint32_t which, uint32_t row, uint32_t col) {
+  const uint32_t h = gemm_matrix_hash(seed, dtype, which);
+  return which == GEN_Q ? attn_q_of(h, row, col)
+                        : which == GEN_KEY ? attn_k_of(h, row, col) : gemm_int_of(h, row, col);
+}
+
+struct AttnExpected {
+  float o, m, l;
+};
+
+// O~[row][d], m[row] and l[row] over N keys, in integer arithmetic only and in
+// one pass: 2^(8 + s - m) = 2^(s + 4) · 2^(4 - m), so the sums are taken with
+// the weights 2^(s + 4) in [1, 256] and shifted once the maximum is known. The
+// shifted sums are the true ones times 2^8, below 2^23 and 2^20.
+GH_HD inline AttnExpected attn_reference(uint32_t seed, int dtype, uint32_t N, uint32_t row,
+                                         uint32_t d) {
+  const uint32_t hq = mix32(gemm_matrix_hash(seed, dtype, GEN_Q) ^ row);  // the row hoisted
+  const uint32_t hk = gemm_matrix_hash(seed, dtype, GEN_KEY);
+  const uint32_t hv = gemm_matrix_hash(seed, dtype, GEN_V);
+  int m = -4;
+  int64_t o = 0, l = 0;
+  for (uint32_t j = 0; j < N; ++j) {
+    const AttnKey k = attn_key_of(hk, j);
+    const int s = k.s1 * ((int)((mix32(hq + k.d1) >> 8) % 5u) - 2) +
+                  k.s2 * ((int)((mix32(hq + k.d2) >> 8) % 5u) - 2);
+    m = s > m ? s : m;
+    l += (int64_t)1 << (s + 4);
+    o += ((int64_t)1 << (s + 4)) * gemm_int_of(hv, j, d);
+  }
+  // |o| << (4 - m) < 2^24 and a multiple of 1: the conversion and the scaling
+  // by 2^-8 are both exact
+  AttnExpected e;
+  e.o = (float)(int32_t)(o * ((int64_t)1 << (4 - m))) * (1.0f / 256.0f);
+  e.m = (float)m;
+  e.l = (float)(int32_t)(l * ((int64_t)1 << (4 - m))) * (1.0f / 256.0f);
+  return e;
+}
+
+// ---------------------------------------------------------------------------
+// Attention check: where a stage lies in LDS, shared by the kernel
+// (gpuhealth_attn.hip) and by tests/native/attn_ref_check.cpp, which shows every
+// address in bounds and every register position the element the MFMA wants.
+//
+// A stage is a block of 64 keys: 8 KiB of K and 8 KiB of V, 64 rows of 128
+// bytes = eight 16-byte chunks, 512 slots per operand. Slot s holds chunk
+// (s % 8) ^ swizzle(row) of row s / 8; the global side fetches what belongs
+// into its slot, as in the GEMM checks.
+//
+// Reads (lane l, i = l & 15, g = l >> 4):
+//   K is the A operand of Sᵀ = K·Qᵀ: lane (i, g) reads K[key][32 ds + 8 g .. + 7]
+//   of key 16 kt + i with one ds_read_b128, the A-read of the GEMM check, and
+//   its swizzle: (row >> 1) & 7 spreads the 16 rows of a read over the banks.
+//   V is the A operand of O~ᵀ += Vᵀ·Pᵀ. The B operand Pᵀ is what the lane holds
+//   of Sᵀ, in register order: k-slot t (0..7) of lane group g in the 32-key
+//   chunk c is key attn_v_key(c, g, t) = 32 c + 16 (t / 4) + 4 g + t % 4, so
+//   Vᵀ has to bring the same keys to the same slots. Half h (slots 4 h .. + 3)
+//   of a fragment is one ds_read_b64_tr_b16 in which lane (i, g) points at
+//   V[32 c + 16 h + 4 g + i / 4][16 dt + 4 (i % 4) .. + 3]; by the lane map of
+//   the read (attn_tr16_source, measured by debug_lds_tr_dump) it receives
+//   V[32 c + 16 h + 4 g + e][16 dt + i], e = 0..3.
+//   V's swizzle, for this pattern and not the GEMM's: one read touches the 16
+//   consecutive rows 32 c + 16 h .. + 15 at one pair of chunks (32 bytes), the
+//   first 32 lanes rows .. + 7. Rows are 128 bytes, half of the 64 banks, so
+//   unswizzled every second row repeats its banks. Bit 0 of the row picks the
+//   half of the banks already; bits 2..1 of the row are xored into the pair
+//   index (bits 2..1 of the chunk), which keeps a pair together and puts the 8
+//   rows of 32 lanes on 8 different pairs of the 64 banks.
+// Correctness does not depend on either swizzle.
+// ---------------------------------------------------------------------------
+constexpr uint32_t kAttnOperandBytes = kAttnBlock * kAttnHeadDim * 2;  // 8 KiB
+constexpr uint32_t kAttnRowBytes = kAttnHeadDim * 2;                   // 128
+
+GH_HD inline uint32_t attn_k_swizzle(uint32_t row) { return (row >> 1) & 7u; }
+GH_HD inline uint32_t attn_v_swizzle(uint32_t row) { return ((row >> 1) & 3u) << 1; }
+
+// what belongs into 16-byte slot `slot` (0..511) of K's and of V's part of a
+// stage: the row of the block and the byte within the row
+GH_HD inline NarrowChunk attn_k_source(uint32_t slot) {
+  const uint32_t row = slot >> 3;
+  return {row, 16u * ((slot & 7u) ^ attn_k_swizzle(row))};
+}
+GH_HD inline NarrowChunk attn_v_source(uint32_t slot) {
+  const uint32_t row = slot >> 3;
+  return {row, 16u * ((slot & 7u) ^ attn_v_swizzle(row))};
+}
+// element offset into K or V (N x 64) of what slot `slot` of key block `block` holds
+GH_HD inline uint64_t attn_global_offset(uint32_t block, NarrowChunk c) {
+  return ((uint64_t)block * kAttnBlock + c.row) * kAttnHeadDim + c.byte / 2u;
+}
+
+// byte offset within K's 8 KiB of the 16 bytes K[row][32 ds + 8 g .. + 7]
+GH_HD inline uint32_t attn_k_read(uint32_t row, uint32_t ds, uint32_t g) {
+  return row * kAttnRowBytes + 16u * ((4u * ds + g) ^ attn_k_swizzle(row));
+}
+
+// the key, within the block, of k-slot t of lane group g in 32-key chunk c
+GH_HD inline uint32_t attn_v_key(uint32_t c, uint32_t g, uint32_t t) {
+  return 32u * c + 16u * (t / 4u) + 4u * g + t % 4u;
+}
+
+// lane map of ds_read_b64_tr_b16: word e (0..3) of lane l's result is word
+// (l & 15) % 4 of what lane (l & ~15) + 4 e + (l & 15) / 4 pointed at; the value
+// is the source as lane * 4 + word
+GH_HD inline uint32_t attn_tr16_source(uint32_t lane, uint32_t e) {
+  const uint32_t i = lane & 15u;
+  return 4u * ((lane & ~15u) + 4u * e + i / 4u) + i % 4u;
+}
+
+// byte offset within V's 8 KiB that lane (i, g) hands to the transposed read
+// for half h of the fragment of chunk c and d-tile dt
+GH_HD inline uint32_t attn_v_read(uint32_t c, uint32_t h, uint32_t dt, uint32_t g, uint32_t i) {
+  const uint32_t row = 32u * c + 16u * h + 4u * g + (i >> 2);
+  const uint32_t col = 16u * dt + 4u * (i & 3u);
+  return row * kAttnRowBytes + 16u * ((col >> 3) ^ attn_v_swizzle(row)) + 2u * (col & 7u);
 }
 
 }  // namespace gh

@@ -375,7 +375,8 @@ def gpu_burn_in_load_seconds(annotations: Optional[Dict[str, str]]) -> Optional[
 def init_gpu_burn_in_startup_probe(ray_container: Container,
                                    load_seconds: Optional[float] = None,
                                    gemm: bool = False,
-                                   gemm_narrow: bool = False) -> None:
+                                   gemm_narrow: bool = False,
+                                   attention: bool = False) -> None:
     """MI355X burn-in as a startupProbe (opt-in, annotation
     ``amd.com/gpu-burn-in: "true"`` on a GPU worker template): the HBM
     pattern sweep and the exact MFMA checks of
@@ -390,7 +391,10 @@ def init_gpu_burn_in_startup_probe(ray_container: Container,
     its two runs took 1.5 ms and 2.1 ms of wall time, fill and check included,
     and three burn-ins with ``--gemm --gemm-narrow`` took 8.04 s to 8.05 s
     against 1.95 s to 8.02 s with ``--gemm`` alone in the same session
-    (docs/benchmarks.md, "GEMM check").
+    (docs/benchmarks.md, "GEMM check"). ``attention`` (annotation
+    ``amd.com/gpu-burn-in-attention: "true"``) adds the attention check after
+    those; its two runs took 2.5 ms each and the timeout stays
+    (docs/benchmarks.md, "Attention check").
     A user-supplied startupProbe is kept."""
     if ray_container.startup_probe is not None:
         return
@@ -403,6 +407,8 @@ def init_gpu_burn_in_startup_probe(ray_container: Container,
         command += " --gemm"
     if gemm_narrow:
         command += " --gemm-narrow"
+    if attention:
+        command += " --attention"
     probe = Probe(
         timeout_seconds=timeout,
         period_seconds=C.GPU_BURN_IN_PROBE_PERIOD_SECONDS,
@@ -843,7 +849,9 @@ def build_pod(
                 gemm=(template.metadata.annotations or {}).get(
                     C.GPU_BURN_IN_GEMM_ANNOTATION_KEY, "").lower() == "true",
                 gemm_narrow=(template.metadata.annotations or {}).get(
-                    C.GPU_BURN_IN_GEMM_NARROW_ANNOTATION_KEY, "").lower() == "true")
+                    C.GPU_BURN_IN_GEMM_NARROW_ANNOTATION_KEY, "").lower() == "true",
+                attention=(template.metadata.annotations or {}).get(
+                    C.GPU_BURN_IN_ATTENTION_ANNOTATION_KEY, "").lower() == "true")
     return pod
 
 

@@ -69,6 +69,9 @@ class HealthReport:
     # narrow GEMM check (fp8, mxfp4) of the burn-in level; None unless asked for
     gemm_narrow_exact: Optional[Dict[str, bool]] = None
     gemm_narrow_faulty: Optional[List[str]] = None
+    # attention check (bf16, f16) of the burn-in level; None unless asked for
+    attn_exact: Optional[Dict[str, bool]] = None
+    attn_faulty: Optional[List[str]] = None
 
 
 def _rocm_smi_ok() -> bool:
@@ -193,10 +196,12 @@ GEMM_NARROW_DTYPES = ("fp8", "mxfp4")
 
 def _gemm_exact(native, device: int, entry: str = "gemm_exact", dtypes=GEMM_DTYPES):
     """The GEMM check at its default shape, once per 16-bit data type; with
-    ``entry="gemm_narrow_exact"`` the narrow one, once per ``GEMM_NARROW_DTYPES``.
-    Returns (ok by data type, faulty, problems)."""
+    ``entry="gemm_narrow_exact"`` the narrow one, once per ``GEMM_NARROW_DTYPES``;
+    with ``entry="attn_exact"`` the attention check, whose result has a head
+    dimension where the GEMM's has k. Returns (ok by data type, faulty, problems)."""
+    what = {"gemm_exact": "gemm", "gemm_narrow_exact": "gemm narrow",
+            "attn_exact": "attention"}[entry]
     if not hasattr(native, entry):
-        what = "gemm" if entry == "gemm_exact" else "gemm narrow"
         return {}, [], [f"{what}: asked for, but this native module has no {entry}"]
     ok, faulty, problems = {}, [], []
     for dtype in dtypes:
@@ -205,7 +210,9 @@ def _gemm_exact(native, device: int, entry: str = "gemm_exact", dtypes=GEMM_DTYP
         if ok[dtype]:
             continue
         faulty.extend(f"{dtype} {_cu_name(f, short=True)}" for f in r["faulty"])
-        problem = f"gemm {dtype} {r['m']}x{r['n']}x{r['k']}: {r['mismatches']} bad elements"
+        depth = r["head_dim"] if entry == "attn_exact" else r["k"]
+        problem = (f"{'attention' if entry == 'attn_exact' else 'gemm'} {dtype} "
+                   f"{r['m']}x{r['n']}x{depth}: {r['mismatches']} bad elements")
         if r["first_bad"] is not None:
             row, col, got, expected = r["first_bad"]
             problem += f", first [{row}][{col}] got {got!r} expected {expected!r}"
@@ -224,7 +231,8 @@ def check_gpu_burn_in(device: int = 0,
                       load_seconds: float = 0.0,
                       mfma_floor_tflops: Optional[Dict[str, float]] = None,
                       gemm: bool = False,
-                      gemm_narrow: bool = False) -> HealthReport:
+                      gemm_narrow: bool = False,
+                      attention: bool = False) -> HealthReport:
     """Burn-in level: the full gate of ``check_gpu_health``, then the exact
     MFMA verification on the bf16, f16, fp8 and MXFP4 data paths, then a
     data-verifying pattern sweep over ``hbm_fraction`` of the free HBM, then
@@ -242,6 +250,12 @@ def check_gpu_burn_in(device: int = 0,
     With ``gemm_narrow`` the same check for fp8 and MXFP4 follows in the GEMM
     check's place: byte and nibble operands through the 8-bit and 4-bit
     transposed LDS reads, MX scales from device memory; reported alike.
+    With ``attention`` the attention check follows the GEMM checks and comes
+    before the MFMA load: one exact bf16 and one exact f16 attention forward
+    with online softmax (fp32 arithmetic on accumulators, ``v_exp_f32``,
+    cross-lane swaps, the packed down-conversion and the accumulator-to-operand
+    hand-over between two MFMAs); reported alike, column 64 of a first bad
+    element being the row maximum and column 65 the row sum.
     Raises GpuHealthError on non-GPU hosts; ``detail`` names what failed."""
     if not gpu_node():
         raise GpuHealthError("not a GPU node (/dev/kfd missing)")
@@ -311,6 +325,14 @@ def check_gpu_burn_in(device: int = 0,
             return _hip_failure(e, rocm_ok)
         problems.extend(narrow_problems)
         healthy = healthy and not narrow_problems
+    attn_ok = attn_faulty = None
+    if attention:
+        try:
+            attn_ok, attn_faulty, attn_problems = _gemm_exact(native, device, "attn_exact")
+        except RuntimeError as e:
+            return _hip_failure(e, rocm_ok)
+        problems.extend(attn_problems)
+        healthy = healthy and not attn_problems
     load_ok = load_by_dtype = load_tflops = load_clock = load_faulty = None
     if load_seconds > 0.0:
         try:
@@ -339,6 +361,7 @@ def check_gpu_burn_in(device: int = 0,
         mfma_load_ok_by_dtype=load_by_dtype,
         gemm_exact=gemm_ok, gemm_faulty=gemm_faulty,
         gemm_narrow_exact=narrow_ok, gemm_narrow_faulty=narrow_faulty,
+        attn_exact=attn_ok, attn_faulty=attn_faulty,
     )
 
 

@@ -24,6 +24,10 @@ fields appear in the output only when it was asked for.
 ``amd.com/gpu-burn-in-gemm-narrow``): the same for fp8 and MXFP4, through the
 8-bit and 4-bit transposed LDS reads with the MX scales from device memory.
 Its fields follow those of ``--gemm``.
+
+``--deep --attention`` adds the attention check (annotation
+``amd.com/gpu-burn-in-attention``): one exact bf16 and one exact f16 attention
+forward with online softmax. Its fields follow those of the GEMM checks.
 """
 from __future__ import annotations
 
@@ -65,11 +69,16 @@ def main(argv=None) -> int:
     parser.add_argument("--gemm-narrow", action="store_true",
                         help="with --deep: the exact fp8 and MXFP4 GEMM check "
                              "through the 8-bit and 4-bit transposed LDS reads")
+    parser.add_argument("--attention", action="store_true",
+                        help="with --deep: the exact attention check, online "
+                             "softmax between two MFMAs")
     args = parser.parse_args(argv)
     if args.gemm and not args.deep:
         parser.error("--gemm needs --deep")
     if args.gemm_narrow and not args.deep:
         parser.error("--gemm-narrow needs --deep")
+    if args.attention and not args.deep:
+        parser.error("--attention needs --deep")
     if args.load_seconds and not args.deep:
         parser.error("--load-seconds needs --deep")
     if args.mfma_floor_tflops and not args.load_seconds:
@@ -95,6 +104,8 @@ def main(argv=None) -> int:
         load["gemm"] = True
     if args.gemm_narrow:
         load["gemm_narrow"] = True
+    if args.attention:
+        load["attention"] = True
 
     try:
         if args.deep:
@@ -135,6 +146,8 @@ def main(argv=None) -> int:
             if args.gemm_narrow:
                 out.update(gemm_narrow_exact=report.gemm_narrow_exact,
                            gemm_narrow_faulty=report.gemm_narrow_faulty)
+            if args.attention:
+                out.update(attn_exact=report.attn_exact, attn_faulty=report.attn_faulty)
             print(json.dumps(out))
         else:
             cu = (f" cu_total={report.cu_total} cu_covered={report.cu_covered} "
@@ -149,6 +162,8 @@ def main(argv=None) -> int:
             if args.gemm_narrow:
                 cu += (f" gemm_narrow_exact={report.gemm_narrow_exact} "
                        f"gemm_narrow_faulty={report.gemm_narrow_faulty}")
+            if args.attention:
+                cu += f" attn_exact={report.attn_exact} attn_faulty={report.attn_faulty}"
             print(f"healthy={report.healthy} mfma_ok={report.mfma_ok} "
                   f"hbm_gb_s={report.hbm_gb_s} rocm_smi_ok={report.rocm_smi_ok} "
                   f"mfma_exact={report.mfma_exact} "

@@ -252,6 +252,8 @@ GPU_BURN_IN_LOAD_PROBE_OVERHEAD_SECONDS = 20
 GPU_BURN_IN_GEMM_ANNOTATION_KEY = "amd.com/gpu-burn-in-gemm"
 # The same for the narrow GEMM check, fp8 and MXFP4 (``--gemm-narrow``).
 GPU_BURN_IN_GEMM_NARROW_ANNOTATION_KEY = "amd.com/gpu-burn-in-gemm-narrow"
+# The same for the attention check, bf16 and f16 (``--attention``).
+GPU_BURN_IN_ATTENTION_ANNOTATION_KEY = "amd.com/gpu-burn-in-attention"
 
 # Device nodes every ROCm container needs (AMD k8s device plugin mounts these
 # automatically when amd.com/gpu is requested; we also support explicit
