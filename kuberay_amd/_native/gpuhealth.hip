@@ -222,12 +222,30 @@
 //                    attn_exact(inject=) into Q, K or V in device memory,
 //                    debug_attn_dump, attn_operand. Details:
 //                    gpuhealth_attn.hip.
+//   * attn_causal_exact — opt-in, single-shot, an entry point of its own: the
+//                    attention check with the causal mask, many heads and head
+//                    dimension 128. Q, K and V [heads · seq, 128], a workgroup
+//                    takes query blocks b and seq / 64 - 1 - b of one head so
+//                    that all walk seq / 64 + 1 key blocks; key blocks above
+//                    the diagonal are not loaded, masked tiles skip their
+//                    MFMAs wave-uniformly and the straddling tile gets -inf per
+//                    element. Stages of 256-byte rows, 64 KiB of LDS, swizzles
+//                    of their own; O~ in 32 accumulator registers. Same data
+//                    and == compare as attn_exact; seq a multiple of 128 up to
+//                    4096, heads · seq up to 131072. Default: seq = 1024 and
+//                    the heads that give every CU two workgroups. Cannot
+//                    show: the final division, a scale, v_exp_f32 off the
+//                    integers, other masks (sliding window, padding), grouped
+//                    K / V heads. Test hooks: attn_causal_exact(inject=),
+//                    debug_attn_causal_dump (also without the mask),
+//                    attn_causal_operand. Details: gpuhealth_attn128.hip.
 //
 // What must agree between host and device (pattern, generators, encoders,
 // reference) is in gpuhealth_ref.hpp. The kernels of gemm_exact ("Burn-in,
 // part 5") and their host code are in gpuhealth_gemm.hip, those of
 // gemm_narrow_exact ("part 6") in gpuhealth_gemm_narrow.hip and those of
-// attn_exact ("part 7") in gpuhealth_attn.hip, translation units of their own
+// attn_exact ("part 7") in gpuhealth_attn.hip and those of attn_causal_exact
+// ("part 8") in gpuhealth_attn128.hip, translation units of their own
 // (the reason is at the top of the first); this file binds them.
 //
 // Build: hipcc --offload-arch=gfx950 (see kuberay_amd/_native/build.py).
@@ -2676,6 +2694,88 @@ static int attn_operand(const std::string& dtype, const std::string& which, int6
                       checked_index(col, gh::kAttnHeadDim, "column"));
 }
 
+// -- causal attention check bindings (Burn-in, part 8: gpuhealth_attn128.hip) --
+// the dict of attn_exact (m = heads * seq, n = seq) plus heads, seq and causal; rows are
+// flat (head * seq + position), first_bad is (row, col, got, expected) with
+// col 0..127 in O~, 128 for m and 129 for l, and a faulty tile is (workgroup, 0)
+static py::dict attn_causal_dict(const ghgemm::Result& r, bool causal) {
+  py::dict d;
+  py::list faulty;
+  for (const ghgemm::FaultyTile& f : r.faulty) {
+    py::dict t = location_dict(f.key);
+    t["tile"] = py::make_tuple(f.tile_row, f.tile_col);
+    t["mismatches"] = f.stats.mismatches;
+    t["first_bad"] = py::make_tuple(f.stats.first_bad / gh::kAttn128OutCols,
+                                    f.stats.first_bad % gh::kAttn128OutCols);
+    faulty.append(t);
+  }
+  d["dtype"] = kDtypeNames[r.dtype];
+  d["m"] = (uint64_t)r.m * r.n;  // as attn_exact: rows of Q, and keys a row's head has
+  d["n"] = r.n;
+  d["heads"] = r.m;
+  d["seq"] = r.n;
+  d["head_dim"] = r.k;
+  d["causal"] = causal;
+  d["ok"] = r.mismatches == 0;
+  d["mismatches"] = r.mismatches;
+  if (r.first_bad >= 0)
+    d["first_bad"] = py::make_tuple(r.first_bad / gh::kAttn128OutCols,
+                                    r.first_bad % gh::kAttn128OutCols, r.got, r.expected);
+  else
+    d["first_bad"] = py::none();
+  d["faulty"] = faulty;
+  d["workgroups"] = r.workgroups;
+  d["cu_total"] = r.cu_total;
+  d["cu_seen"] = r.cu_seen;
+  d["elapsed_ms"] = r.elapsed_ms;
+  // for information: one cold launch, the key-block steps walked (the tiles
+  // skipped inside a diagonal block counted in), nothing is gated on it
+  const double steps = (double)r.workgroups * (causal ? r.n / 64.0 + 1.0 : r.n / 32.0);
+  const double flop = 4.0 * 64.0 * 64.0 * (double)r.k * steps;
+  d["tflops"] = r.elapsed_ms > 0.0 ? flop / (r.elapsed_ms * 1e-3) / 1e12 : 0.0;
+  return d;
+}
+
+static py::dict attn_causal_exact(int device, const std::string& dtype, int64_t heads, int64_t seq,
+                                  uint32_t seed, inject_attn_t inject) {
+  const int dt = parse_attn_dtype(dtype);
+  const std::optional<ghgemm::AttnInject> inj = checked_attn_inject(inject);
+  use_device(device);
+  return attn_causal_dict(
+      ghgemm::run_attn128_exact(dt, heads, seq, true, seed, inj ? &*inj : nullptr), true);
+}
+
+// test hook: the raw Q, K, V, O~, m and l of the same fill, inject and launch;
+// causal=False is the same kernel without the mask
+static py::dict debug_attn_causal_dump(int device, const std::string& dtype, int64_t heads,
+                                       int64_t seq, bool causal, uint32_t seed,
+                                       inject_attn_t inject) {
+  const int dt = parse_attn_dtype(dtype);
+  const std::optional<ghgemm::AttnInject> inj = checked_attn_inject(inject);
+  use_device(device);
+  ghgemm::AttnDump dump;
+  (void)ghgemm::run_attn128_exact(dt, heads, seq, causal, seed, inj ? &*inj : nullptr, &dump);
+  py::dict d;
+  d["q"] = py::bytes(dump.q);
+  d["k"] = py::bytes(dump.k);
+  d["v"] = py::bytes(dump.v);
+  d["o"] = py::bytes(dump.o);
+  d["m"] = py::bytes(dump.m);
+  d["l"] = py::bytes(dump.l);
+  return d;
+}
+
+static int attn_causal_operand(const std::string& dtype, const std::string& which, int64_t row,
+                               int64_t col, uint32_t seed) {
+  const int dt = parse_attn_dtype(dtype);
+  if (which != "q" && which != "k" && which != "v")
+    throw py::value_error("which must be q, k or v (got '" + which + "')");
+  return gh::gen_attn128(seed, dt,
+                         which == "q" ? gh::GEN_Q : which == "k" ? gh::GEN_KEY : gh::GEN_V,
+                         checked_index(row, 1ull << 32, "row"),
+                         checked_index(col, gh::kAttn128HeadDim, "column"));
+}
+
 static std::vector<std::vector<int>> debug_permlane_dump(int device) {
   use_device(device);
   return ghgemm::run_debug_permlane_dump();
@@ -2806,6 +2906,18 @@ PYBIND11_MODULE(gpuhealth, m) {
         py::arg("inject") = py::none());
   m.def("attn_operand", &attn_operand, py::arg("dtype"), py::arg("which"), py::arg("row"),
         py::arg("col"), py::arg("seed") = gh::kDefaultSeed);
+  m.attr("ATTN_CAUSAL_HEAD_DIM") = gh::kAttn128HeadDim;
+  m.attr("ATTN_CAUSAL_MAX_SEQ") = gh::kAttn128MaxL;
+  m.attr("ATTN_CAUSAL_DEFAULT_SEQ") = ghgemm::kAttn128DefaultL;
+  m.def("attn_causal_exact", &attn_causal_exact, py::arg("device") = 0,
+        py::arg("dtype") = "bf16", py::arg("heads") = 0, py::arg("seq") = 0,
+        py::arg("seed") = gh::kDefaultSeed, py::arg("inject") = py::none());
+  m.def("debug_attn_causal_dump", &debug_attn_causal_dump, py::arg("device") = 0,
+        py::arg("dtype") = "bf16", py::arg("heads") = 1, py::arg("seq") = 128,
+        py::arg("causal") = true, py::arg("seed") = gh::kDefaultSeed,
+        py::arg("inject") = py::none());
+  m.def("attn_causal_operand", &attn_causal_operand, py::arg("dtype"), py::arg("which"),
+        py::arg("row"), py::arg("col"), py::arg("seed") = gh::kDefaultSeed);
   m.def("debug_permlane_dump", &debug_permlane_dump, py::arg("device") = 0);
   m.def("debug_exp2_dump", &debug_exp2_dump, py::arg("device") = 0);
   m.def("flop_per_mfma", [](const std::string& dtype) {

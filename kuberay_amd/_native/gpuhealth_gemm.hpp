@@ -1,6 +1,7 @@
 // gpuhealth_gemm — what gpuhealth.hip (bindings) and gpuhealth_gemm.hip
 // (kernels and their host code) share of the burn-in's GEMM check, and below
-// that what it shares with gpuhealth_gemm_narrow.hip and gpuhealth_attn.hip: plain
+// that what it shares with gpuhealth_gemm_narrow.hip, gpuhealth_attn.hip and
+// gpuhealth_attn128.hip: plain
 // structs and a few functions, no HIP and no pybind11 types. The files are
 // separate translation units so that the GEMM kernels can be compiled with a
 // switch of their own (kuberay_amd/_native/build.py) while every older kernel
@@ -140,5 +141,28 @@ std::vector<std::vector<int>> run_debug_permlane_dump();
 
 // v_exp_f32 of 0, -1, .., -126 and of -inf: 128 values
 std::vector<float> run_debug_exp2_dump();
+
+// --- the causal attention check at head dimension 128 (gpuhealth_attn128.hip) --
+
+constexpr uint32_t kAttn128DefaultL = 1024;
+
+// Unnormalised multi-head attention forward with online softmax on the current
+// device: Q, K and V are [heads · L, 128], head h in rows h·L .. h·L + L - 1;
+// with causal a query sees the keys of its head up to its own position, without
+// (a debug setting) all L of them. 0 takes the default: L = kAttn128DefaultL,
+// heads = what gives kWorkgroupsPerCu workgroups of L / 128 a head to every CU,
+// rounded up. In the Result m is the number of heads, n is L and k the head
+// dimension; a faulty tile is a workgroup (tile_row = head · L / 128 + pair,
+// tile_col = 0), which computes query blocks pair and L / 64 - 1 - pair of its
+// head; first_bad is row * gh::kAttn128OutCols + col over the flat rows, where
+// col 0..127 is O~, 128 is m and 129 is l. The inject and the dump are those of
+// run_attn_exact, rows counted flat. Throws std::invalid_argument for L that
+// is no positive multiple of 128 or above gh::kAttn128MaxL (exactness), heads
+// below 1, heads · L above gh::kAttn128MaxRows (a bound on what one call
+// allocates), a data type other than bf16 / f16 and an inject outside its
+// matrix or with a mask wider than 16 bits; std::runtime_error for a failing
+// HIP call.
+Result run_attn128_exact(int dtype, int64_t heads, int64_t L, bool causal, uint32_t seed,
+                         const AttnInject* inject = nullptr, AttnDump* dump = nullptr);
 
 }  // namespace ghgemm

@@ -6,9 +6,10 @@
 // MFMA check, the encoders to bf16 / f16 / OCP e4m3 / e2m1 bit patterns, the
 // exact reference product, the matrix generator and reference of the GEMM
 // checks, and the generators, the premise, the integer reference and the LDS
-// address functions of the attention check. No HIP, no pybind11 — the programs
-// under tests/native/ (gpuhealth_ref_check.cpp, gemm_ref_check.cpp,
-// gemm_narrow_ref_check.cpp, attn_ref_check.cpp) drive it as stand-alone g++
+// address functions of the attention check and of the causal one at head
+// dimension 128. No HIP, no pybind11 — the programs under tests/native/
+// (gpuhealth_ref_check.cpp, gemm_ref_check.cpp, gemm_narrow_ref_check.cpp,
+// attn_ref_check.cpp, attn128_ref_check.cpp) drive it as stand-alone g++
 // programs.
 //
 // Exactness premise: bf16 / f16 / fp8 operands are integers in [-8, 8], so a
@@ -787,6 +788,177 @@ GH_HD inline uint32_t attn_v_read(uint32_t c, uint32_t h, uint32_t dt, uint32_t 
   const uint32_t row = 32u * c + 16u * h + 4u * g + (i >> 2);
   const uint32_t col = 16u * dt + 4u * (i & 3u);
   return row * kAttnRowBytes + 16u * ((col >> 3) ^ attn_v_swizzle(row)) + 2u * (col & 7u);
+}
+
+// ---------------------------------------------------------------------------
+// Causal attention check: H heads of sequence length L at head dimension 128
+//
+// Q, K and V are [H·L, 128] row-major bf16 or f16, head h in rows h·L .. h·L +
+// L - 1; O~ [H·L, 128], m and l [H·L] are fp32. With i and j the positions of a
+// query and a key within their head,
+//   s_ij = Q[hL + i]·K[hL + j],  visible(i, j) = !causal || j <= i,
+//   m[i] = max over visible j of s_ij,  l[i] = Σ over visible j of 2^(s_ij - m_i),
+//   O~[i][d] = Σ over visible j of 2^(s_ij - m_i) · V[hL + j][d]
+// Scale 1, base 2, no final division. The generators are those of the check
+// above over 128 columns, hashed from the flat row h·L + i, so heads differ:
+// Q dense in [-2, 2] (attn_q_of), V dense in [-8, 8] (gemm_int_of), K two-hot
+// with ±1 at two distinct columns of 128 (attn128_key_of), under the same
+// GEN_Q, GEN_KEY and GEN_V.
+//
+// Exactness premise, restated for the mask. A masked key contributes exactly 0
+// to l and to O~ and does not take part in m: on the device its score is -inf,
+// v_max_f32 ignores it next to a finite value and v_exp_f32 turns it into +0
+// (measured by debug_exp2_dump), which bf16 and f16 hold exactly. Every visible
+// s is an integer in [-4, 4], so the argument of the check above holds for the
+// visible keys alone: a running maximum is the maximum of the visible keys seen
+// so far, every p is 0 or a power of two in [2^-8, 1], every partial l and O~
+// is a multiple of 2^-8 of magnitude at most L and 8 L <= 2^15 for L <=
+// kAttn128MaxL = 4096: at most 23 significant bits, exact in fp32 in any
+// order, and a rescale is exact because its result is such a sum again. Key 0
+// of a head is visible to every query of it, so the visible set is never empty,
+// m is finite and the first key block of a row always raises m_run from -inf
+// to a finite value: -inf - -inf does not occur. Shown on the device for the
+// hashed data at L = 4096 (tests/test_gpu_attn_causal.py); for other data of
+// the same range it is argued from the bound.
+// ---------------------------------------------------------------------------
+constexpr uint32_t kAttn128HeadDim = 128;
+constexpr uint32_t kAttn128Block = 64;    // queries of a query block, and keys of a stage
+constexpr uint32_t kAttn128MaxL = 4096;   // 8 L * 2^8 <= 2^23
+// heads · L at most; not needed for exactness: bounds what one call allocates,
+// 1288 bytes a row of Q, K, V, O~, m and l together, 161 MiB at the cap
+constexpr uint32_t kAttn128MaxRows = 1u << 17;
+constexpr uint32_t kAttn128OutCols = kAttn128HeadDim + 2;  // O~, then m, then l
+
+GH_HD inline AttnKey attn128_key_of(uint32_t matrix_hash, uint32_t row) {
+  const uint32_t h = mix32(matrix_hash ^ row);
+  AttnKey k;
+  k.d1 = (h >> 8) & 127u;
+  k.d2 = (k.d1 + 1u + (h >> 15) % 127u) & 127u;  // d1 + 1 .. d1 + 127 mod 128: never d1
+  k.s1 = (h >> 24) & 1u ? -1 : 1;
+  k.s2 = (h >> 25) & 1u ? -1 : 1;
+  return k;
+}
+GH_HD inline int attn128_k_of(uint32_t matrix_hash, uint32_t row, uint32_t col) {
+  const AttnKey k = attn128_key_of(matrix_hash, row);
+  return col == k.d1 ? k.s1 : col == k.d2 ? k.s2 : 0;
+}
+
+// Q, K or V of the causal check at flat row h·L + i; which is GEN_Q, GEN_KEY or GEN_V
+GH_HD inline int gen_attn128(uint32_t seed, int dtype, uint32_t which, uint32_t row, uint32_t col) {
+  const uint32_t h = gemm_matrix_hash(seed, dtype, which);
+  return which == GEN_Q ? attn_q_of(h, row, col)
+                        : which == GEN_KEY ? attn128_k_of(h, row, col) : gemm_int_of(h, row, col);
+}
+
+// O~[row][d], m[row] and l[row] of flat row `row` = h·L + i over the visible
+// keys of head h, in integer arithmetic and one pass, as attn_reference
+GH_HD inline AttnExpected attn128_reference(uint32_t seed, int dtype, uint32_t L, bool causal,
+                                            uint32_t row, uint32_t d) {
+  const uint32_t hq = mix32(gemm_matrix_hash(seed, dtype, GEN_Q) ^ row);  // the row hoisted
+  const uint32_t hk = gemm_matrix_hash(seed, dtype, GEN_KEY);
+  const uint32_t hv = gemm_matrix_hash(seed, dtype, GEN_V);
+  const uint32_t first = row - row % L, keys = causal ? row % L + 1u : L;
+  int m = -4;
+  int64_t o = 0, l = 0;
+  for (uint32_t j = first; j < first + keys; ++j) {
+    const AttnKey k = attn128_key_of(hk, j);
+    const int s = k.s1 * ((int)((mix32(hq + k.d1) >> 8) % 5u) - 2) +
+                  k.s2 * ((int)((mix32(hq + k.d2) >> 8) % 5u) - 2);
+    m = s > m ? s : m;
+    l += (int64_t)1 << (s + 4);
+    o += ((int64_t)1 << (s + 4)) * gemm_int_of(hv, j, d);
+  }
+  AttnExpected e;
+  e.o = (float)(int32_t)(o * ((int64_t)1 << (4 - m))) * (1.0f / 256.0f);
+  e.m = (float)m;
+  e.l = (float)(int32_t)(l * ((int64_t)1 << (4 - m))) * (1.0f / 256.0f);
+  return e;
+}
+
+// ---------------------------------------------------------------------------
+// Causal attention check: where a stage lies in LDS, shared by the kernel
+// (gpuhealth_attn128.hip) and by tests/native/attn128_ref_check.cpp.
+//
+// A stage is a block of 64 keys: 16 KiB of K and 16 KiB of V, 64 rows of 256
+// bytes = sixteen 16-byte chunks, 1024 slots per operand. Slot s holds chunk
+// (s % 16) ^ swizzle(row) of row s / 16; the global side fetches what belongs
+// into its slot. A wave's load of 64 slots is four whole rows, so the global
+// side still reads whole 256-byte lines whatever the swizzle.
+//
+// A 256-byte row is all 64 banks once, so unswizzled every row repeats the
+// banks of the row above and the swizzles for 128-byte rows, which count on
+// bit 0 of the row to pick a half of the banks, do not carry over.
+//
+// Reads (lane l, i = l & 15, g = l >> 4):
+//   K is the A operand of Sᵀ = K·Qᵀ: lane (i, g) reads K[key][32 ds + 8 g .. + 7]
+//   of key 16 kt + i with one ds_read_b128, ds = 0..3: chunk 4 ds + g. The 16
+//   lanes of a group g read one chunk index in 16 consecutive rows, 256 bytes
+//   in all; xoring the low four bits of the row into the chunk index sends the
+//   16 rows to 16 different chunks, which are the 64 banks once.
+//   V is the A operand of O~ᵀ += Vᵀ·Pᵀ in P's register order (attn_v_key): half
+//   h of the fragment of 32-key chunk c and d-tile dt (0..7) is one
+//   ds_read_b64_tr_b16 in which lane (i, g) points at
+//   V[32 c + 16 h + 4 g + i / 4][16 dt + 4 (i % 4) .. + 3] and by the lane map
+//   (attn_tr16_source) receives V[32 c + 16 h + 4 g + e][16 dt + i]. One read
+//   touches the 16 consecutive rows 32 c + 16 h .. + 15 at one pair of chunks
+//   (chunks 2 dt and 2 dt + 1, 32 bytes), the first 32 lanes rows .. + 7. A row
+//   has 8 such pairs; xoring the low three bits of the row into the pair index
+//   (bits 3..1 of the chunk) keeps a pair together and puts the 8 rows of 32
+//   lanes on the 8 different pairs, the 64 banks once.
+// That the reads are conflict-free is argued here, not measured. Correctness
+// does not depend on either swizzle: staging and reads go through the same
+// function, and any function into 0..15 gives the same data.
+// ---------------------------------------------------------------------------
+constexpr uint32_t kAttn128RowBytes = kAttn128HeadDim * 2;                     // 256
+constexpr uint32_t kAttn128OperandBytes = kAttn128Block * kAttn128RowBytes;    // 16 KiB
+constexpr uint32_t kAttn128Slots = kAttn128OperandBytes / 16;                  // 1024
+
+GH_HD inline uint32_t attn128_k_swizzle(uint32_t row) { return row & 15u; }
+GH_HD inline uint32_t attn128_v_swizzle(uint32_t row) { return (row & 7u) << 1; }
+
+// what belongs into 16-byte slot `slot` (0..1023) of K's and of V's part of a
+// stage: the row of the key block and the byte within the row
+GH_HD inline NarrowChunk attn128_k_source(uint32_t slot) {
+  const uint32_t row = slot >> 4;
+  return {row, 16u * ((slot & 15u) ^ attn128_k_swizzle(row))};
+}
+GH_HD inline NarrowChunk attn128_v_source(uint32_t slot) {
+  const uint32_t row = slot >> 4;
+  return {row, 16u * ((slot & 15u) ^ attn128_v_swizzle(row))};
+}
+// element offset into K or V ([H·L, 128]) of chunk c of the key block that
+// starts at flat row `first_row`
+GH_HD inline uint64_t attn128_global_offset(uint32_t first_row, NarrowChunk c) {
+  return ((uint64_t)first_row + c.row) * kAttn128HeadDim + c.byte / 2u;
+}
+
+// byte offset within K's 16 KiB of the 16 bytes K[row][32 ds + 8 g .. + 7]
+GH_HD inline uint32_t attn128_k_read(uint32_t row, uint32_t ds, uint32_t g) {
+  return row * kAttn128RowBytes + 16u * ((4u * ds + g) ^ attn128_k_swizzle(row));
+}
+
+// byte offset within V's 16 KiB that lane (i, g) hands to the transposed read
+// for half h of the fragment of chunk c and d-tile dt (0..7)
+GH_HD inline uint32_t attn128_v_read(uint32_t c, uint32_t h, uint32_t dt, uint32_t g, uint32_t i) {
+  const uint32_t row = 32u * c + 16u * h + 4u * g + (i >> 2);
+  const uint32_t col = 16u * dt + 4u * (i & 3u);
+  return row * kAttn128RowBytes + 16u * ((col >> 3) ^ attn128_v_swizzle(row)) + 2u * (col & 7u);
+}
+
+// The work split of the causal check: workgroup `pair` (0 .. nb / 2 - 1) of a
+// head takes query blocks pair and nb - 1 - pair, nb = L / 64, one after the
+// other. Query block qb walks key blocks 0 .. qb under the mask and all nb
+// without: nb + 1 or 2 nb key-block steps a workgroup.
+GH_HD inline uint32_t attn128_query_block(uint32_t nb, uint32_t pair, uint32_t phase) {
+  return phase ? nb - 1u - pair : pair;
+}
+GH_HD inline uint32_t attn128_key_blocks(uint32_t nb, uint32_t qb, bool causal) {
+  return causal ? qb + 1u : nb;
+}
+// the workgroup, counted over all heads, that computes flat row `row`
+GH_HD inline uint32_t attn128_workgroup_of(uint32_t L, uint32_t row) {
+  const uint32_t nb = L / kAttn128Block, qb = row % L / kAttn128Block;
+  return row / L * (nb / 2u) + (qb < nb - 1u - qb ? qb : nb - 1u - qb);
 }
 
 }  // namespace gh

@@ -376,7 +376,8 @@ def init_gpu_burn_in_startup_probe(ray_container: Container,
                                    load_seconds: Optional[float] = None,
                                    gemm: bool = False,
                                    gemm_narrow: bool = False,
-                                   attention: bool = False) -> None:
+                                   attention: bool = False,
+                                   attention_causal: bool = False) -> None:
     """MI355X burn-in as a startupProbe (opt-in, annotation
     ``amd.com/gpu-burn-in: "true"`` on a GPU worker template): the HBM
     pattern sweep and the exact MFMA checks of
@@ -394,7 +395,12 @@ def init_gpu_burn_in_startup_probe(ray_container: Container,
     (docs/benchmarks.md, "GEMM check"). ``attention`` (annotation
     ``amd.com/gpu-burn-in-attention: "true"``) adds the attention check after
     those; its two runs took 2.5 ms each and the timeout stays
-    (docs/benchmarks.md, "Attention check").
+    (docs/benchmarks.md, "Attention check"). ``attention_causal`` (annotation
+    ``amd.com/gpu-burn-in-attention-causal: "true"``) adds the causal
+    attention check at head dimension 128 after that one; its two runs took
+    9 ms of wall time each, three burn-ins with it took 8.05 s to 8.06 s
+    against 8.04 s without in the same session, and the timeout stays
+    (docs/benchmarks.md, "Causal attention check").
     A user-supplied startupProbe is kept."""
     if ray_container.startup_probe is not None:
         return
@@ -409,6 +415,8 @@ def init_gpu_burn_in_startup_probe(ray_container: Container,
         command += " --gemm-narrow"
     if attention:
         command += " --attention"
+    if attention_causal:
+        command += " --attention-causal"
     probe = Probe(
         timeout_seconds=timeout,
         period_seconds=C.GPU_BURN_IN_PROBE_PERIOD_SECONDS,
@@ -851,7 +859,9 @@ def build_pod(
                 gemm_narrow=(template.metadata.annotations or {}).get(
                     C.GPU_BURN_IN_GEMM_NARROW_ANNOTATION_KEY, "").lower() == "true",
                 attention=(template.metadata.annotations or {}).get(
-                    C.GPU_BURN_IN_ATTENTION_ANNOTATION_KEY, "").lower() == "true")
+                    C.GPU_BURN_IN_ATTENTION_ANNOTATION_KEY, "").lower() == "true",
+                attention_causal=(template.metadata.annotations or {}).get(
+                    C.GPU_BURN_IN_ATTENTION_CAUSAL_ANNOTATION_KEY, "").lower() == "true")
     return pod
 
 

@@ -72,6 +72,9 @@ class HealthReport:
     # attention check (bf16, f16) of the burn-in level; None unless asked for
     attn_exact: Optional[Dict[str, bool]] = None
     attn_faulty: Optional[List[str]] = None
+    # causal attention check at head dimension 128; None unless asked for
+    attn_causal_exact: Optional[Dict[str, bool]] = None
+    attn_causal_faulty: Optional[List[str]] = None
 
 
 def _rocm_smi_ok() -> bool:
@@ -198,9 +201,11 @@ def _gemm_exact(native, device: int, entry: str = "gemm_exact", dtypes=GEMM_DTYP
     """The GEMM check at its default shape, once per 16-bit data type; with
     ``entry="gemm_narrow_exact"`` the narrow one, once per ``GEMM_NARROW_DTYPES``;
     with ``entry="attn_exact"`` the attention check, whose result has a head
-    dimension where the GEMM's has k. Returns (ok by data type, faulty, problems)."""
+    dimension where the GEMM's has k; with ``entry="attn_causal_exact"`` the
+    causal one, whose shape is heads x seq x head dimension. Returns (ok by
+    data type, faulty, problems)."""
     what = {"gemm_exact": "gemm", "gemm_narrow_exact": "gemm narrow",
-            "attn_exact": "attention"}[entry]
+            "attn_exact": "attention", "attn_causal_exact": "attention causal"}[entry]
     if not hasattr(native, entry):
         return {}, [], [f"{what}: asked for, but this native module has no {entry}"]
     ok, faulty, problems = {}, [], []
@@ -210,9 +215,13 @@ def _gemm_exact(native, device: int, entry: str = "gemm_exact", dtypes=GEMM_DTYP
         if ok[dtype]:
             continue
         faulty.extend(f"{dtype} {_cu_name(f, short=True)}" for f in r["faulty"])
-        depth = r["head_dim"] if entry == "attn_exact" else r["k"]
-        problem = (f"{'attention' if entry == 'attn_exact' else 'gemm'} {dtype} "
-                   f"{r['m']}x{r['n']}x{depth}: {r['mismatches']} bad elements")
+        if entry == "attn_causal_exact":  # heads x seq x head dimension, rows flat
+            problem = (f"attention causal {dtype} {r['heads']}x{r['seq']}x{r['head_dim']}: "
+                       f"{r['mismatches']} bad elements")
+        else:
+            depth = r["head_dim"] if entry == "attn_exact" else r["k"]
+            problem = (f"{'attention' if entry == 'attn_exact' else 'gemm'} {dtype} "
+                       f"{r['m']}x{r['n']}x{depth}: {r['mismatches']} bad elements")
         if r["first_bad"] is not None:
             row, col, got, expected = r["first_bad"]
             problem += f", first [{row}][{col}] got {got!r} expected {expected!r}"
@@ -232,7 +241,8 @@ def check_gpu_burn_in(device: int = 0,
                       mfma_floor_tflops: Optional[Dict[str, float]] = None,
                       gemm: bool = False,
                       gemm_narrow: bool = False,
-                      attention: bool = False) -> HealthReport:
+                      attention: bool = False,
+                      attention_causal: bool = False) -> HealthReport:
     """Burn-in level: the full gate of ``check_gpu_health``, then the exact
     MFMA verification on the bf16, f16, fp8 and MXFP4 data paths, then a
     data-verifying pattern sweep over ``hbm_fraction`` of the free HBM, then
@@ -256,6 +266,11 @@ def check_gpu_burn_in(device: int = 0,
     cross-lane swaps, the packed down-conversion and the accumulator-to-operand
     hand-over between two MFMAs); reported alike, column 64 of a first bad
     element being the row maximum and column 65 the row sum.
+    With ``attention_causal`` the causal attention check follows that one:
+    the same forward for many heads at head dimension 128 under the causal
+    mask (256-byte LDS rows, ``-inf`` through ``v_max_f32`` and ``v_exp_f32``,
+    wave-uniform skips of masked tiles); reported alike over the flat rows
+    head x seq + position, columns 128 and 129 being the maximum and the sum.
     Raises GpuHealthError on non-GPU hosts; ``detail`` names what failed."""
     if not gpu_node():
         raise GpuHealthError("not a GPU node (/dev/kfd missing)")
@@ -333,6 +348,15 @@ def check_gpu_burn_in(device: int = 0,
             return _hip_failure(e, rocm_ok)
         problems.extend(attn_problems)
         healthy = healthy and not attn_problems
+    causal_ok = causal_faulty = None
+    if attention_causal:
+        try:
+            causal_ok, causal_faulty, causal_problems = _gemm_exact(
+                native, device, "attn_causal_exact")
+        except RuntimeError as e:
+            return _hip_failure(e, rocm_ok)
+        problems.extend(causal_problems)
+        healthy = healthy and not causal_problems
     load_ok = load_by_dtype = load_tflops = load_clock = load_faulty = None
     if load_seconds > 0.0:
         try:
@@ -362,6 +386,7 @@ def check_gpu_burn_in(device: int = 0,
         gemm_exact=gemm_ok, gemm_faulty=gemm_faulty,
         gemm_narrow_exact=narrow_ok, gemm_narrow_faulty=narrow_faulty,
         attn_exact=attn_ok, attn_faulty=attn_faulty,
+        attn_causal_exact=causal_ok, attn_causal_faulty=causal_faulty,
     )
 
 

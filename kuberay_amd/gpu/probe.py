@@ -28,6 +28,11 @@ Its fields follow those of ``--gemm``.
 ``--deep --attention`` adds the attention check (annotation
 ``amd.com/gpu-burn-in-attention``): one exact bf16 and one exact f16 attention
 forward with online softmax. Its fields follow those of the GEMM checks.
+
+``--deep --attention-causal`` adds the causal attention check (annotation
+``amd.com/gpu-burn-in-attention-causal``): the same forward for many heads at
+head dimension 128 under the causal mask. Its fields follow those of
+``--attention``.
 """
 from __future__ import annotations
 
@@ -72,6 +77,9 @@ def main(argv=None) -> int:
     parser.add_argument("--attention", action="store_true",
                         help="with --deep: the exact attention check, online "
                              "softmax between two MFMAs")
+    parser.add_argument("--attention-causal", action="store_true",
+                        help="with --deep: the exact causal attention check, "
+                             "many heads at head dimension 128")
     args = parser.parse_args(argv)
     if args.gemm and not args.deep:
         parser.error("--gemm needs --deep")
@@ -79,6 +87,8 @@ def main(argv=None) -> int:
         parser.error("--gemm-narrow needs --deep")
     if args.attention and not args.deep:
         parser.error("--attention needs --deep")
+    if args.attention_causal and not args.deep:
+        parser.error("--attention-causal needs --deep")
     if args.load_seconds and not args.deep:
         parser.error("--load-seconds needs --deep")
     if args.mfma_floor_tflops and not args.load_seconds:
@@ -106,6 +116,8 @@ def main(argv=None) -> int:
         load["gemm_narrow"] = True
     if args.attention:
         load["attention"] = True
+    if args.attention_causal:
+        load["attention_causal"] = True
 
     try:
         if args.deep:
@@ -148,6 +160,9 @@ def main(argv=None) -> int:
                            gemm_narrow_faulty=report.gemm_narrow_faulty)
             if args.attention:
                 out.update(attn_exact=report.attn_exact, attn_faulty=report.attn_faulty)
+            if args.attention_causal:
+                out.update(attn_causal_exact=report.attn_causal_exact,
+                           attn_causal_faulty=report.attn_causal_faulty)
             print(json.dumps(out))
         else:
             cu = (f" cu_total={report.cu_total} cu_covered={report.cu_covered} "
@@ -164,6 +179,9 @@ def main(argv=None) -> int:
                        f"gemm_narrow_faulty={report.gemm_narrow_faulty}")
             if args.attention:
                 cu += f" attn_exact={report.attn_exact} attn_faulty={report.attn_faulty}"
+            if args.attention_causal:
+                cu += (f" attn_causal_exact={report.attn_causal_exact} "
+                       f"attn_causal_faulty={report.attn_causal_faulty}")
             print(f"healthy={report.healthy} mfma_ok={report.mfma_ok} "
                   f"hbm_gb_s={report.hbm_gb_s} rocm_smi_ok={report.rocm_smi_ok} "
                   f"mfma_exact={report.mfma_exact} "

@@ -187,9 +187,9 @@ class OperatorMetrics:
         for dtype, ok in (getattr(report, "mfma_load_ok_by_dtype", None) or {}).items():
             self.gpu_burn_in_ok.labels(node, f"mfma_load_{dtype}").set(1 if ok else 0)
         # the GEMM check's, only when the report has them
-        # and the attention check's
+        # and the attention checks'
         for field, check in (("gemm_exact", "gemm"), ("gemm_narrow_exact", "gemm"),
-                             ("attn_exact", "attn")):
+                             ("attn_exact", "attn"), ("attn_causal_exact", "attn_causal")):
             for dtype, ok in (getattr(report, field, None) or {}).items():
                 self.gpu_burn_in_ok.labels(node, f"{check}_{dtype}").set(1 if ok else 0)
 

@@ -254,6 +254,9 @@ GPU_BURN_IN_GEMM_ANNOTATION_KEY = "amd.com/gpu-burn-in-gemm"
 GPU_BURN_IN_GEMM_NARROW_ANNOTATION_KEY = "amd.com/gpu-burn-in-gemm-narrow"
 # The same for the attention check, bf16 and f16 (``--attention``).
 GPU_BURN_IN_ATTENTION_ANNOTATION_KEY = "amd.com/gpu-burn-in-attention"
+# The same for the causal attention check at head dimension 128
+# (``--attention-causal``).
+GPU_BURN_IN_ATTENTION_CAUSAL_ANNOTATION_KEY = "amd.com/gpu-burn-in-attention-causal"
 
 # Device nodes every ROCm container needs (AMD k8s device plugin mounts these
 # automatically when amd.com/gpu is requested; we also support explicit
