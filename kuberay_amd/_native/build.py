@@ -4,8 +4,8 @@ live next to the sources so it travels to GPU boxes with the repo snapshot).
 Extensions:
   * gpuhealth  — HIP/gfx950 on-device health probes and burn-in
                  (gpuhealth.hip, gpuhealth_gemm.hip, gpuhealth_gemm_narrow.hip,
-                 gpuhealth_attn.hip and gpuhealth_attn128.hip over
-                 gpuhealth_ref.hpp)
+                 gpuhealth_attn.hip, gpuhealth_attn128.hip and
+                 gpuhealth_attn_decode.hip over gpuhealth_ref.hpp)
   * engine     — C++ control-plane core: object cache + indices + native
                  JSON encoding and decoding and model-tree copies (engine.cpp
                  bindings over store_core.hpp, json_decode.hpp and
@@ -47,7 +47,8 @@ def _needs_rebuild(src: Path, out: Path, *deps: Path) -> bool:
 def build_gpuhealth(force: bool = False) -> Path:
     src = HERE / "gpuhealth.hip"
     gemm_srcs = [HERE / "gpuhealth_gemm.hip", HERE / "gpuhealth_gemm_narrow.hip",
-                 HERE / "gpuhealth_attn.hip", HERE / "gpuhealth_attn128.hip"]
+                 HERE / "gpuhealth_attn.hip", HERE / "gpuhealth_attn128.hip",
+                 HERE / "gpuhealth_attn_decode.hip"]
     out = HERE / f"gpuhealth{_ext_suffix()}"
     if not force and not _needs_rebuild(src, out, *gemm_srcs, HERE / "gpuhealth_ref.hpp",
                                         HERE / "gpuhealth_gemm.hpp",

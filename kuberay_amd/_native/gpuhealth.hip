@@ -239,13 +239,32 @@
 //                    K / V heads. Test hooks: attn_causal_exact(inject=),
 //                    debug_attn_causal_dump (also without the mask),
 //                    attn_causal_operand. Details: gpuhealth_attn128.hip.
+//   * attn_decode_exact — opt-in, single-shot, an entry point of its own: the
+//                    attention an LLM replica decodes with. One query token a
+//                    sequence, `group` query heads a KV head (GQA) as the N
+//                    side of the MFMA, K and V in a paged cache of 16-token
+//                    pages found through a block table whose map scatters
+//                    neighbouring pages, contexts that end inside a page next
+//                    to poisoned slots, the context split over `splits`
+//                    workgroups whose four waves run decoupled on two pages
+//                    each and reduce through LDS, and a second kernel that
+//                    merges the splits' partial softmax states, empty ones
+//                    included. Finals and split partials compare with ==.
+//                    ctx up to 4096; default: 8 KV heads of 8 query heads,
+//                    max_ctx 2048, 4 splits and the batch that gives every CU
+//                    two workgroups. Cannot show: the final division, a
+//                    scale, other page sizes, fp8 caches. Test hooks:
+//                    attn_decode_exact(inject=) into Q, K, V or the block
+//                    table, debug_attn_decode_dump, attn_decode_operand.
+//                    Details: gpuhealth_attn_decode.hip.
 //
 // What must agree between host and device (pattern, generators, encoders,
 // reference) is in gpuhealth_ref.hpp. The kernels of gemm_exact ("Burn-in,
 // part 5") and their host code are in gpuhealth_gemm.hip, those of
 // gemm_narrow_exact ("part 6") in gpuhealth_gemm_narrow.hip and those of
-// attn_exact ("part 7") in gpuhealth_attn.hip and those of attn_causal_exact
-// ("part 8") in gpuhealth_attn128.hip, translation units of their own
+// attn_exact ("part 7") in gpuhealth_attn.hip, those of attn_causal_exact
+// ("part 8") in gpuhealth_attn128.hip and those of attn_decode_exact ("part
+// 9") in gpuhealth_attn_decode.hip, translation units of their own
 // (the reason is at the top of the first); this file binds them.
 //
 // Build: hipcc --offload-arch=gfx950 (see kuberay_amd/_native/build.py).
@@ -2776,6 +2795,113 @@ static int attn_causal_operand(const std::string& dtype, const std::string& whic
                          checked_index(col, gh::kAttn128HeadDim, "column"));
 }
 
+// -- decode attention check bindings (Burn-in, part 9: gpuhealth_attn_decode.hip) --
+// (target "q", "k", "v" or "table", row, col, xor mask); for "table" row is the
+// sequence and col its logical page; the place is checked by run_attn_decode_exact
+static std::optional<ghgemm::AttnInject> checked_decode_inject(const inject_attn_t& in) {
+  if (!in || std::get<0>(*in) != "table") return checked_attn_inject(in);
+  ghgemm::AttnInject inj;
+  inj.which = ghgemm::ATTN_TABLE;
+  inj.row = checked_index(std::get<1>(*in), 1ull << 32, "injected sequence");
+  inj.col = checked_index(std::get<2>(*in), 1ull << 32, "injected page");
+  inj.mask = checked_index(std::get<3>(*in), 1ull << 32, "xor mask");
+  return inj;
+}
+
+typedef std::optional<std::vector<int64_t>> decode_ctx_t;
+
+// the dict of attn_causal_exact (m = rows of Q, n = max_ctx) plus batch, kv_heads,
+// group, splits, max_ctx and kv_bytes; rows are flat ((b * kv_heads + hk) * group +
+// g). A faulty tile is (b * kv_heads + hk, split) with the CU it ran on, or (..,
+// splits) without one: bad finals over clean partials, the merge.
+static py::dict attn_decode_dict(const ghgemm::DecodeResult& r) {
+  py::dict d;
+  py::list faulty;
+  for (const ghgemm::FaultyTile& f : r.faulty) {
+    py::dict t = f.key == ghgemm::kDecodeNoCu ? py::dict() : location_dict(f.key);
+    t["tile"] = py::make_tuple(f.tile_row, f.tile_col);
+    t["mismatches"] = f.stats.mismatches;
+    t["first_bad"] = py::make_tuple(f.stats.first_bad / gh::kAttn128OutCols,
+                                    f.stats.first_bad % gh::kAttn128OutCols);
+    faulty.append(t);
+  }
+  d["dtype"] = kDtypeNames[r.dtype];
+  d["m"] = r.m;
+  d["n"] = r.n;
+  d["batch"] = r.batch;
+  d["kv_heads"] = r.kv_heads;
+  d["group"] = r.group;
+  d["splits"] = r.splits;
+  d["max_ctx"] = r.max_ctx;
+  d["head_dim"] = r.k;
+  d["kv_bytes"] = r.kv_bytes;
+  d["ok"] = r.mismatches == 0;
+  d["mismatches"] = r.mismatches;
+  if (r.first_bad >= 0)
+    d["first_bad"] = py::make_tuple(r.first_bad / gh::kAttn128OutCols,
+                                    r.first_bad % gh::kAttn128OutCols, r.got, r.expected);
+  else
+    d["first_bad"] = py::none();
+  d["faulty"] = faulty;
+  d["workgroups"] = r.workgroups;
+  d["cu_total"] = r.cu_total;
+  d["cu_seen"] = r.cu_seen;
+  d["elapsed_ms"] = r.elapsed_ms;
+  d["merge_ms"] = r.merge_ms;
+  // for information: one cold launch of the main kernel, nothing is gated on it
+  d["gb_s"] = r.elapsed_ms > 0.0 ? (double)r.kv_bytes / (r.elapsed_ms * 1e-3) / 1e9 : 0.0;
+  return d;
+}
+
+static py::dict attn_decode_exact(int device, const std::string& dtype, int64_t batch,
+                                  int64_t kv_heads, int64_t group, int64_t max_ctx, int64_t splits,
+                                  decode_ctx_t ctx, uint32_t seed, inject_attn_t inject) {
+  const int dt = parse_attn_dtype(dtype);
+  const std::optional<ghgemm::AttnInject> inj = checked_decode_inject(inject);
+  use_device(device);
+  return attn_decode_dict(ghgemm::run_attn_decode_exact(
+      dt, batch, kv_heads, group, max_ctx, splits, ctx ? *ctx : std::vector<int64_t>(), seed,
+      inj ? &*inj : nullptr));
+}
+
+// test hook: the raw Q, pools, table, ctx, split partials and finals of the
+// same fill, inject and launches
+static py::dict debug_attn_decode_dump(int device, const std::string& dtype, int64_t batch,
+                                       int64_t kv_heads, int64_t group, int64_t max_ctx,
+                                       int64_t splits, decode_ctx_t ctx, uint32_t seed,
+                                       inject_attn_t inject) {
+  const int dt = parse_attn_dtype(dtype);
+  const std::optional<ghgemm::AttnInject> inj = checked_decode_inject(inject);
+  use_device(device);
+  ghgemm::DecodeDump dump;
+  (void)ghgemm::run_attn_decode_exact(dt, batch, kv_heads, group, max_ctx, splits,
+                                      ctx ? *ctx : std::vector<int64_t>(), seed,
+                                      inj ? &*inj : nullptr, &dump);
+  py::dict d;
+  d["q"] = py::bytes(dump.q);
+  d["k_pool"] = py::bytes(dump.k_pool);
+  d["v_pool"] = py::bytes(dump.v_pool);
+  d["table"] = py::bytes(dump.table);
+  d["ctx"] = py::bytes(dump.ctx);
+  d["partial"] = py::bytes(dump.partial);
+  d["o"] = py::bytes(dump.o);
+  d["m"] = py::bytes(dump.m);
+  d["l"] = py::bytes(dump.l);
+  return d;
+}
+
+// Q at its flat row, K and V at the logical row kv_row * ATTN_DECODE_MAX_CTX + position
+static int attn_decode_operand(const std::string& dtype, const std::string& which, int64_t row,
+                               int64_t col, uint32_t seed) {
+  const int dt = parse_attn_dtype(dtype);
+  if (which != "q" && which != "k" && which != "v")
+    throw py::value_error("which must be q, k or v (got '" + which + "')");
+  return gh::gen_decode(seed, dt,
+                        which == "q" ? gh::GEN_Q : which == "k" ? gh::GEN_KEY : gh::GEN_V,
+                        checked_index(row, 1ull << 32, "row"),
+                        checked_index(col, gh::kAttn128HeadDim, "column"));
+}
+
 static std::vector<std::vector<int>> debug_permlane_dump(int device) {
   use_device(device);
   return ghgemm::run_debug_permlane_dump();
@@ -2917,6 +3043,23 @@ PYBIND11_MODULE(gpuhealth, m) {
         py::arg("causal") = true, py::arg("seed") = gh::kDefaultSeed,
         py::arg("inject") = py::none());
   m.def("attn_causal_operand", &attn_causal_operand, py::arg("dtype"), py::arg("which"),
+        py::arg("row"), py::arg("col"), py::arg("seed") = gh::kDefaultSeed);
+  m.attr("ATTN_DECODE_PAGE_TOKENS") = gh::kDecodePageTokens;
+  m.attr("ATTN_DECODE_MAX_CTX") = gh::kDecodeMaxCtx;
+  m.attr("ATTN_DECODE_DEFAULT_CTX") = ghgemm::kDecodeDefaultCtx;
+  m.attr("ATTN_DECODE_DEFAULT_SPLITS") = ghgemm::kDecodeDefaultSplits;
+  m.attr("ATTN_DECODE_POISON") = gh::kDecodePoison;
+  m.def("attn_decode_exact", &attn_decode_exact, py::arg("device") = 0,
+        py::arg("dtype") = "bf16", py::arg("batch") = 0, py::arg("kv_heads") = 0,
+        py::arg("group") = 0, py::arg("max_ctx") = 0, py::arg("splits") = 0,
+        py::arg("ctx") = py::none(), py::arg("seed") = gh::kDefaultSeed,
+        py::arg("inject") = py::none());
+  m.def("debug_attn_decode_dump", &debug_attn_decode_dump, py::arg("device") = 0,
+        py::arg("dtype") = "bf16", py::arg("batch") = 0, py::arg("kv_heads") = 1,
+        py::arg("group") = 8, py::arg("max_ctx") = 128, py::arg("splits") = 1,
+        py::arg("ctx") = py::none(), py::arg("seed") = gh::kDefaultSeed,
+        py::arg("inject") = py::none());
+  m.def("attn_decode_operand", &attn_decode_operand, py::arg("dtype"), py::arg("which"),
         py::arg("row"), py::arg("col"), py::arg("seed") = gh::kDefaultSeed);
   m.def("debug_permlane_dump", &debug_permlane_dump, py::arg("device") = 0);
   m.def("debug_exp2_dump", &debug_exp2_dump, py::arg("device") = 0);

@@ -1,7 +1,7 @@
 // gpuhealth_gemm — what gpuhealth.hip (bindings) and gpuhealth_gemm.hip
 // (kernels and their host code) share of the burn-in's GEMM check, and below
-// that what it shares with gpuhealth_gemm_narrow.hip, gpuhealth_attn.hip and
-// gpuhealth_attn128.hip: plain
+// that what it shares with gpuhealth_gemm_narrow.hip, gpuhealth_attn.hip,
+// gpuhealth_attn128.hip and gpuhealth_attn_decode.hip: plain
 // structs and a few functions, no HIP and no pybind11 types. The files are
 // separate translation units so that the GEMM kernels can be compiled with a
 // switch of their own (kuberay_amd/_native/build.py) while every older kernel
@@ -164,5 +164,59 @@ constexpr uint32_t kAttn128DefaultL = 1024;
 // HIP call.
 Result run_attn128_exact(int dtype, int64_t heads, int64_t L, bool causal, uint32_t seed,
                          const AttnInject* inject = nullptr, AttnDump* dump = nullptr);
+
+// --- the decode attention check: paged KV, GQA, split-KV (gpuhealth_attn_decode.hip) --
+
+constexpr uint32_t kDecodeDefaultCtx = 2048;
+constexpr uint32_t kDecodeDefaultGroup = 8;
+constexpr uint32_t kDecodeDefaultKvHeads = 8;
+constexpr uint32_t kDecodeDefaultSplits = 4;
+// the place of a faulty tile that is no workgroup: the merge over splits
+constexpr uint32_t kDecodeNoCu = ~0u;
+
+// AttnInject's fourth target: one block-table entry, row = sequence, col =
+// logical page, xored with a non-zero mask below the pool size, so that the
+// kernel reads a wrong page inside the pool. For ATTN_Q the row is the flat Q
+// row, for ATTN_K and ATTN_V the logical row gh::decode_kv_row of an owned
+// position; the host finds the slot through the clean table.
+constexpr int ATTN_TABLE = 3;
+
+struct DecodeResult : Result {
+  uint32_t batch = 0, kv_heads = 0, group = 0, splits = 0, max_ctx = 0;
+  uint64_t kv_bytes = 0;   // K and V rows one launch reads
+  double merge_ms = 0.0;   // the merge kernel; elapsed_ms is the main kernel
+};
+
+struct DecodeDump {
+  std::string q, k_pool, v_pool, table, ctx, partial, o, m, l;
+};
+
+// Unnormalised decode attention on the current device: one query token for
+// each of batch sequences, kv_heads KV heads with `group` query heads each
+// (1, 2, 4, 8 or 16), over a paged KV cache of 16-token pages found through a
+// block table, the context of sequence b being ctx[b] in [1, max_ctx], max_ctx
+// at most gh::kDecodeMaxCtx (exactness); `splits` workgroups (1 .. 32) share a
+// (sequence, KV head) and a second kernel merges them. 0 takes the default:
+// group = 8, kv_heads = 8, max_ctx = kDecodeDefaultCtx, splits =
+// kDecodeDefaultSplits, batch = the length of ctx or, ctx being empty, what
+// gives every CU kWorkgroupsPerCu workgroups; an empty ctx takes
+// gh::decode_default_ctx. In the Result m is the number of Q rows, n is
+// max_ctx and k the head dimension; first_bad is row * gh::kAttn128OutCols +
+// col over the finals, which alone decide mismatches. A faulty tile is
+// (b · kv_heads + hk, split) for a workgroup whose partial is bad, and
+// (b · kv_heads + hk, splits) with key kDecodeNoCu for a KV row whose finals
+// are bad while its partials are clean: the merge. Throws
+// std::invalid_argument for anything outside these ranges, batch · kv_heads
+// above gh::kDecodeMaxKvRows, pools above gh::kDecodeMaxPoolBytes (a bound on
+// what one call allocates), a ctx list of the wrong length or with an entry
+// outside [1, max_ctx], a data type other than bf16 / f16 and an inject
+// outside what the check owns or with a mask that is zero, wider than 16 bits
+// or, for the table, not below the pool size; std::runtime_error for a failing
+// HIP call.
+DecodeResult run_attn_decode_exact(int dtype, int64_t batch, int64_t kv_heads, int64_t group,
+                                   int64_t max_ctx, int64_t splits,
+                                   const std::vector<int64_t>& ctx, uint32_t seed,
+                                   const AttnInject* inject = nullptr,
+                                   DecodeDump* dump = nullptr);
 
 }  // namespace ghgemm

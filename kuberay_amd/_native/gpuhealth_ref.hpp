@@ -6,11 +6,11 @@
 // MFMA check, the encoders to bf16 / f16 / OCP e4m3 / e2m1 bit patterns, the
 // exact reference product, the matrix generator and reference of the GEMM
 // checks, and the generators, the premise, the integer reference and the LDS
-// address functions of the attention check and of the causal one at head
-// dimension 128. No HIP, no pybind11 — the programs under tests/native/
-// (gpuhealth_ref_check.cpp, gemm_ref_check.cpp, gemm_narrow_ref_check.cpp,
-// attn_ref_check.cpp, attn128_ref_check.cpp) drive it as stand-alone g++
-// programs.
+// address functions of the attention check, of the causal one at head
+// dimension 128 and of the paged decode one. No HIP, no pybind11 — the programs
+// under tests/native/ (gpuhealth_ref_check.cpp, gemm_ref_check.cpp,
+// gemm_narrow_ref_check.cpp, attn_ref_check.cpp, attn128_ref_check.cpp,
+// attn_decode_ref_check.cpp) drive it as stand-alone g++ programs.
 //
 // Exactness premise: bf16 / f16 / fp8 operands are integers in [-8, 8], so a
 // K=32 dot product plus C is an integer below 2^12; MXFP4 operands are e2m1
@@ -959,6 +959,191 @@ GH_HD inline uint32_t attn128_key_blocks(uint32_t nb, uint32_t qb, bool causal) 
 GH_HD inline uint32_t attn128_workgroup_of(uint32_t L, uint32_t row) {
   const uint32_t nb = L / kAttn128Block, qb = row % L / kAttn128Block;
   return row / L * (nb / 2u) + (qb < nb - 1u - qb ? qb : nb - 1u - qb);
+}
+
+// ---------------------------------------------------------------------------
+// Decode attention check: one query token a sequence over a paged KV cache,
+// grouped-query heads, the context split over workgroups (split-KV)
+//
+// For sequence b, KV head hk and query head hq = hk·G + g, flat Q row
+// (b·kv_heads + hk)·G + g:
+//   keys j = 0 .. ctx[b] - 1 of (b, hk), found through the block table
+//   s_j = Q[row]·K[b][hk][j],  m = max_j s_j,  l = Σ_j 2^(s_j - m),
+//   O~[d] = Σ_j 2^(s_j - m) · V[b][hk][j][d]
+// Scale 1, base 2, head dimension 128, no final division.
+//
+// Cache: pages of kDecodePageTokens = 16 tokens. The pools are [pages,
+// kv_heads, 16, 128] 16-bit for K and for V, so a (page, head) tile is 16
+// contiguous rows of 256 bytes, 4 KiB. The block table is [batch, max_pages]
+// int32, max_pages = ceil(max_ctx / 16). The pool has decode_pool_pages =
+// the power of two at or above batch · max_pages pages, and logical page
+// b · max_pages + p lies at decode_page_of: an affine map modulo the pool with
+// an odd multiplier from the seed (5 modulo 16), a bijection of the pool that
+// never puts neighbouring logical pages next to each other.
+//
+// Generators: Q dense in [-2, 2] (attn_q_of at the flat Q row), K two-hot ±1
+// (attn128_key_of) and V dense in [-8, 8] (gemm_int_of), both at logical row
+// (b · kv_heads + hk) · kDecodeMaxCtx + position, under GEN_Q, GEN_KEY, GEN_V:
+// the data does not depend on where the table put it, and the check needs no
+// table to recompute it.
+//
+// Exactness premise, restated. Every token slot that no sequence owns (the
+// tail of a sequence's last page, and every page beyond it or mapped to no
+// sequence) holds kDecodePoison = 0x7700: 28672 as f16 and 2^111 as bf16, a
+// large finite number in both, small enough that a 128-term dot product with
+// |q| <= 2 stays finite in fp32. A kernel that forgets the mask takes poison
+// into m, l or O~ and fails loudly. A correct kernel overwrites the score of
+// such a key with -inf before the maximum (a select, no arithmetic on the
+// poisoned score), p = exp2(-inf - finite) = +0, and 0 · poison = 0 exactly:
+// the poisoned V row adds nothing. Pages wholly past ctx are not read at all.
+// Every visible s is an integer in [-4, 4], so what the checks above argue
+// holds for any subset of a row's keys under that subset's own maximum: a
+// per-wave partial (the keys of one wave of one workgroup) and a split partial
+// (the steps of one workgroup) are sums of powers of two in [2^-8, 1] times
+// integers in [-8, 8], multiples of 2^-8 of magnitude at most 8·ctx <= 2^15.
+// A rescale by 2^(m_part - m) with m the maximum of a superset keeps it a
+// multiple of 2^-8 of at most that magnitude, because the whole row's score
+// range is at most 8: at most 23 significant bits, exact in fp32 in any order.
+// An empty part (a wave or a split that saw no key) has m = -inf, l = 0, O~ =
+// 0 and is merged with exp2(-inf - finite) = 0. Hence finals and split
+// partials compare with == against integer arithmetic for ctx <=
+// kDecodeMaxCtx = 4096. Shown on the device for the hashed data at ctx = 4096
+// (tests/test_gpu_attn_decode.py); for other data argued from the bound.
+// ---------------------------------------------------------------------------
+constexpr uint32_t kDecodePageTokens = 16;
+constexpr uint32_t kDecodeMaxCtx = 4096;     // 8 N * 2^8 <= 2^23
+constexpr uint32_t kDecodeStepKeys = 128;    // a workgroup's step: 8 pages, 2 a wave
+constexpr uint32_t kDecodeStepPages = kDecodeStepKeys / kDecodePageTokens;
+constexpr uint32_t kDecodeMaxGroup = 16;     // the N side of one 16x16x32 MFMA
+constexpr uint32_t kDecodeMaxSplits = kDecodeMaxCtx / kDecodeStepKeys;  // 32: a step a split
+constexpr uint32_t kDecodePoison = 0x7700u;
+constexpr uint32_t kDecodePageElems = kDecodePageTokens * kAttn128HeadDim;  // of one head
+// K and V pools together at most; not needed for exactness: bounds what one call allocates
+constexpr uint64_t kDecodeMaxPoolBytes = 1ull << 30;
+// batch · kv_heads at most: the logical K / V row fits 32 bits and a grid dimension holds it
+constexpr uint32_t kDecodeMaxKvRows = 1u << 15;
+
+GH_HD inline uint32_t decode_pages(uint32_t ctx) {
+  return (ctx + kDecodePageTokens - 1u) / kDecodePageTokens;
+}
+GH_HD inline uint32_t decode_pool_pages(uint32_t batch, uint32_t max_pages) {
+  uint32_t pool = 1;
+  while (pool < batch * max_pages) pool <<= 1;
+  return pool;
+}
+// physical page of logical page `logical` = b · max_pages + p; pool_pages a power of two
+GH_HD inline uint32_t decode_page_of(uint32_t seed, uint32_t pool_pages, uint32_t logical) {
+  // 5 modulo 16: odd, and two neighbours are never fewer than 5 pages apart
+  const uint32_t mult = (mix32(seed ^ 0x50A6E5u) & ~15u) | 5u, add = mix32(seed ^ 0x0FF5E7u);
+  return (mult * logical + add) & (pool_pages - 1u);
+}
+// ctx[b] when the caller gives none: sequence 0 the full max_ctx, the rest
+// hashed into [1, max_ctx], not rounded to a page
+GH_HD inline uint32_t decode_default_ctx(uint32_t seed, uint32_t b, uint32_t max_ctx) {
+  return b == 0 ? max_ctx : 1u + mix32(mix32(seed ^ 0xC7C7C7u) + b) % max_ctx;
+}
+// the logical K / V row of position `pos` of KV row kvrow = b · kv_heads + hk
+GH_HD inline uint32_t decode_kv_row(uint32_t kvrow, uint32_t pos) {
+  return kvrow * kDecodeMaxCtx + pos;
+}
+// Q[row][col] at the flat Q row, K or V[kvrow][pos][col] at row = decode_kv_row
+GH_HD inline int gen_decode(uint32_t seed, int dtype, uint32_t which, uint32_t row, uint32_t col) {
+  return gen_attn128(seed, dtype, which, row, col);
+}
+
+// The work split: a sequence has ns = decode_steps(ctx) steps of 128 keys, and
+// split s of S takes steps decode_split_first(ns, S, s) .. (ns, S, s + 1) - 1,
+// none at all where S > ns.
+GH_HD inline uint32_t decode_steps(uint32_t ctx) {
+  return (ctx + kDecodeStepKeys - 1u) / kDecodeStepKeys;
+}
+GH_HD inline uint32_t decode_split_first(uint32_t ns, uint32_t S, uint32_t s) { return s * ns / S; }
+// the keys of split s of S of a sequence of ctx keys: [first, end), empty when first == end
+GH_HD inline uint32_t decode_split_key(uint32_t ctx, uint32_t S, uint32_t s) {
+  const uint32_t key = decode_split_first(decode_steps(ctx), S, s) * kDecodeStepKeys;
+  return key < ctx ? key : ctx;
+}
+
+// O~[row][d], m[row] and l[row] of flat Q row `row` over keys key_first ..
+// key_end - 1 of its KV row, in integer arithmetic and one pass, as
+// attn_reference: the whole context for a final, a split's keys for a partial.
+// No key at all gives m = -inf, l = 0, O~ = 0.
+GH_HD inline AttnExpected decode_reference(uint32_t seed, int dtype, uint32_t group, uint32_t row,
+                                           uint32_t d, uint32_t key_first, uint32_t key_end) {
+  AttnExpected e;
+  if (key_first >= key_end) {
+    e.o = 0.f, e.m = -__builtin_inff(), e.l = 0.f;
+    return e;
+  }
+  const uint32_t hq = mix32(gemm_matrix_hash(seed, dtype, GEN_Q) ^ row);  // the row hoisted
+  const uint32_t hk = gemm_matrix_hash(seed, dtype, GEN_KEY);
+  const uint32_t hv = gemm_matrix_hash(seed, dtype, GEN_V);
+  const uint32_t base = decode_kv_row(row / group, 0);
+  int m = -4;
+  int64_t o = 0, l = 0;
+  for (uint32_t j = base + key_first; j < base + key_end; ++j) {
+    const AttnKey k = attn128_key_of(hk, j);
+    const int s = k.s1 * ((int)((mix32(hq + k.d1) >> 8) % 5u) - 2) +
+                  k.s2 * ((int)((mix32(hq + k.d2) >> 8) % 5u) - 2);
+    m = s > m ? s : m;
+    l += (int64_t)1 << (s + 4);
+    o += ((int64_t)1 << (s + 4)) * gemm_int_of(hv, j, d);
+  }
+  e.o = (float)(int32_t)(o * ((int64_t)1 << (4 - m))) * (1.0f / 256.0f);
+  e.m = (float)m;
+  e.l = (float)(int32_t)(l * ((int64_t)1 << (4 - m))) * (1.0f / 256.0f);
+  return e;
+}
+
+// ---------------------------------------------------------------------------
+// Decode attention check: LDS addresses, shared by the kernel
+// (gpuhealth_attn_decode.hip) and by tests/native/attn_decode_ref_check.cpp.
+//
+// A workgroup is four waves and 64 KiB of LDS: wave w owns bytes 16384 w ..
+// + 16383, two stages of 8 KiB. A stage is the wave's two pages of V of one
+// step, 32 rows (row 16 t + token of page t) of 256 bytes, 512 slots of 16
+// bytes; slot s holds chunk (s % 16) ^ swizzle(row) of row s / 16, and the
+// global side fetches what belongs into its slot. K does not pass through LDS.
+//
+// The V read is that of the causal check with one 32-key chunk: rows of 256
+// bytes, half h of a fragment one ds_read_b64_tr_b16 over the 16 consecutive
+// rows 16 h .. + 15 (page h) at one pair of chunks. The derivation of
+// attn128_v_swizzle speaks of exactly that and carries over unchanged, so the
+// functions below are attn128_v_source and attn128_v_read at chunk 0. Argued,
+// not measured, and correctness does not depend on it.
+//
+// Epilogue: the stages are free, and wave w lays its partial into its own
+// 16 KiB: O~ᵀ[d][query i] as fp32 at 4 (16 d + i), 8 KiB, then m[i] and l[i].
+// The stores of the four lane groups fall on the same banks four at a time;
+// it is one pass a workgroup and left so.
+// ---------------------------------------------------------------------------
+constexpr uint32_t kDecodeWaves = 4;
+constexpr uint32_t kDecodeStageBytes = 2 * kDecodePageTokens * kAttn128RowBytes;  // 8 KiB
+constexpr uint32_t kDecodeStageSlots = kDecodeStageBytes / 16;                    // 512
+constexpr uint32_t kDecodeWaveBytes = 2 * kDecodeStageBytes;                      // 16 KiB
+constexpr uint32_t kDecodeLdsBytes = kDecodeWaves * kDecodeWaveBytes;             // 64 KiB
+
+GH_HD inline uint32_t decode_stage_base(uint32_t wave, uint32_t buf) {
+  return wave * kDecodeWaveBytes + buf * kDecodeStageBytes;
+}
+// what belongs into slot `slot` (0..511) of a stage: row = 16 · page of the wave + token
+GH_HD inline NarrowChunk decode_v_source(uint32_t slot) { return attn128_v_source(slot); }
+// element offset into a pool of [token][col] of head hk of physical page `page`
+GH_HD inline uint64_t decode_pool_offset(uint32_t page, uint32_t kv_heads, uint32_t hk,
+                                         uint32_t token, uint32_t col) {
+  return (((uint64_t)page * kv_heads + hk) * kDecodePageTokens + token) * kAttn128HeadDim + col;
+}
+// byte offset within a stage that lane (i, g) hands to the transposed read for
+// half h (page h of the wave) of the fragment of d-tile dt
+GH_HD inline uint32_t decode_v_read(uint32_t h, uint32_t dt, uint32_t g, uint32_t i) {
+  return attn128_v_read(0, h, dt, g, i);
+}
+// the epilogue's places, byte offsets into the workgroup's LDS
+GH_HD inline uint32_t decode_epi_o(uint32_t wave, uint32_t d, uint32_t i) {
+  return wave * kDecodeWaveBytes + 4u * (16u * d + i);
+}
+GH_HD inline uint32_t decode_epi_ml(uint32_t wave, uint32_t which, uint32_t i) {  // 0: m, 1: l
+  return wave * kDecodeWaveBytes + kDecodeStageBytes + 64u * which + 4u * i;
 }
 
 }  // namespace gh

@@ -377,7 +377,8 @@ def init_gpu_burn_in_startup_probe(ray_container: Container,
                                    gemm: bool = False,
                                    gemm_narrow: bool = False,
                                    attention: bool = False,
-                                   attention_causal: bool = False) -> None:
+                                   attention_causal: bool = False,
+                                   attention_decode: bool = False) -> None:
     """MI355X burn-in as a startupProbe (opt-in, annotation
     ``amd.com/gpu-burn-in: "true"`` on a GPU worker template): the HBM
     pattern sweep and the exact MFMA checks of
@@ -400,7 +401,12 @@ def init_gpu_burn_in_startup_probe(ray_container: Container,
     attention check at head dimension 128 after that one; its two runs took
     9 ms of wall time each, three burn-ins with it took 8.05 s to 8.06 s
     against 8.04 s without in the same session, and the timeout stays
-    (docs/benchmarks.md, "Causal attention check").
+    (docs/benchmarks.md, "Causal attention check"). ``attention_decode``
+    (annotation ``amd.com/gpu-burn-in-attention-decode: "true"``) adds the
+    decode attention check (paged KV cache, GQA, split-KV) after that one; its
+    two runs took 2 ms of wall time each, burn-ins with it took 8.03 s and
+    8.05 s against 8.03 s without in the same process, and the timeout stays
+    (docs/benchmarks.md, "Decode attention check").
     A user-supplied startupProbe is kept."""
     if ray_container.startup_probe is not None:
         return
@@ -417,6 +423,8 @@ def init_gpu_burn_in_startup_probe(ray_container: Container,
         command += " --attention"
     if attention_causal:
         command += " --attention-causal"
+    if attention_decode:
+        command += " --attention-decode"
     probe = Probe(
         timeout_seconds=timeout,
         period_seconds=C.GPU_BURN_IN_PROBE_PERIOD_SECONDS,
@@ -861,7 +869,9 @@ def build_pod(
                 attention=(template.metadata.annotations or {}).get(
                     C.GPU_BURN_IN_ATTENTION_ANNOTATION_KEY, "").lower() == "true",
                 attention_causal=(template.metadata.annotations or {}).get(
-                    C.GPU_BURN_IN_ATTENTION_CAUSAL_ANNOTATION_KEY, "").lower() == "true")
+                    C.GPU_BURN_IN_ATTENTION_CAUSAL_ANNOTATION_KEY, "").lower() == "true",
+                attention_decode=(template.metadata.annotations or {}).get(
+                    C.GPU_BURN_IN_ATTENTION_DECODE_ANNOTATION_KEY, "").lower() == "true")
     return pod
 
 

@@ -75,6 +75,9 @@ class HealthReport:
     # causal attention check at head dimension 128; None unless asked for
     attn_causal_exact: Optional[Dict[str, bool]] = None
     attn_causal_faulty: Optional[List[str]] = None
+    # decode attention check (paged KV, GQA, split-KV); None unless asked for
+    attn_decode_exact: Optional[Dict[str, bool]] = None
+    attn_decode_faulty: Optional[List[str]] = None
 
 
 def _rocm_smi_ok() -> bool:
@@ -134,6 +137,8 @@ DEFAULT_BURN_IN_HBM_FRACTION = 0.9
 
 
 def _cu_name(where, short: bool = False) -> str:
+    if "cu" not in where:  # the decode check's merge over splits: a kernel, no one CU
+        return "merge"
     if short:
         return f"xcc{where['xcc']}/se{where['se']}/cu{where['cu']}"
     return f"xcc{where['xcc']}/se{where['se']}/sh{where['sh']}/cu{where['cu']}"
@@ -202,10 +207,13 @@ def _gemm_exact(native, device: int, entry: str = "gemm_exact", dtypes=GEMM_DTYP
     ``entry="gemm_narrow_exact"`` the narrow one, once per ``GEMM_NARROW_DTYPES``;
     with ``entry="attn_exact"`` the attention check, whose result has a head
     dimension where the GEMM's has k; with ``entry="attn_causal_exact"`` the
-    causal one, whose shape is heads x seq x head dimension. Returns (ok by
-    data type, faulty, problems)."""
+    causal one, whose shape is heads x seq x head dimension; with
+    ``entry="attn_decode_exact"`` the decode one, whose shape is batch x
+    kv_heads x group and the context. Returns (ok by data type, faulty,
+    problems)."""
     what = {"gemm_exact": "gemm", "gemm_narrow_exact": "gemm narrow",
-            "attn_exact": "attention", "attn_causal_exact": "attention causal"}[entry]
+            "attn_exact": "attention", "attn_causal_exact": "attention causal",
+            "attn_decode_exact": "attention decode"}[entry]
     if not hasattr(native, entry):
         return {}, [], [f"{what}: asked for, but this native module has no {entry}"]
     ok, faulty, problems = {}, [], []
@@ -218,6 +226,9 @@ def _gemm_exact(native, device: int, entry: str = "gemm_exact", dtypes=GEMM_DTYP
         if entry == "attn_causal_exact":  # heads x seq x head dimension, rows flat
             problem = (f"attention causal {dtype} {r['heads']}x{r['seq']}x{r['head_dim']}: "
                        f"{r['mismatches']} bad elements")
+        elif entry == "attn_decode_exact":  # rows flat: (sequence, KV head, query head)
+            problem = (f"attention decode {dtype} {r['batch']}x{r['kv_heads']}x{r['group']} "
+                       f"ctx {r['max_ctx']}: {r['mismatches']} bad elements")
         else:
             depth = r["head_dim"] if entry == "attn_exact" else r["k"]
             problem = (f"{'attention' if entry == 'attn_exact' else 'gemm'} {dtype} "
@@ -242,7 +253,8 @@ def check_gpu_burn_in(device: int = 0,
                       gemm: bool = False,
                       gemm_narrow: bool = False,
                       attention: bool = False,
-                      attention_causal: bool = False) -> HealthReport:
+                      attention_causal: bool = False,
+                      attention_decode: bool = False) -> HealthReport:
     """Burn-in level: the full gate of ``check_gpu_health``, then the exact
     MFMA verification on the bf16, f16, fp8 and MXFP4 data paths, then a
     data-verifying pattern sweep over ``hbm_fraction`` of the free HBM, then
@@ -271,6 +283,11 @@ def check_gpu_burn_in(device: int = 0,
     mask (256-byte LDS rows, ``-inf`` through ``v_max_f32`` and ``v_exp_f32``,
     wave-uniform skips of masked tiles); reported alike over the flat rows
     head x seq + position, columns 128 and 129 being the maximum and the sum.
+    With ``attention_decode`` the decode attention check follows that one: one
+    query token a sequence over a paged KV cache through a block table,
+    grouped-query heads, the context split over workgroups and merged by a
+    second kernel; reported alike over the flat rows (sequence x kv_heads + KV
+    head) x group + query head, a bad merge being named ``merge`` for a CU.
     Raises GpuHealthError on non-GPU hosts; ``detail`` names what failed."""
     if not gpu_node():
         raise GpuHealthError("not a GPU node (/dev/kfd missing)")
@@ -357,6 +374,15 @@ def check_gpu_burn_in(device: int = 0,
             return _hip_failure(e, rocm_ok)
         problems.extend(causal_problems)
         healthy = healthy and not causal_problems
+    decode_ok = decode_faulty = None
+    if attention_decode:
+        try:
+            decode_ok, decode_faulty, decode_problems = _gemm_exact(
+                native, device, "attn_decode_exact")
+        except RuntimeError as e:
+            return _hip_failure(e, rocm_ok)
+        problems.extend(decode_problems)
+        healthy = healthy and not decode_problems
     load_ok = load_by_dtype = load_tflops = load_clock = load_faulty = None
     if load_seconds > 0.0:
         try:
@@ -387,6 +413,7 @@ def check_gpu_burn_in(device: int = 0,
         gemm_narrow_exact=narrow_ok, gemm_narrow_faulty=narrow_faulty,
         attn_exact=attn_ok, attn_faulty=attn_faulty,
         attn_causal_exact=causal_ok, attn_causal_faulty=causal_faulty,
+        attn_decode_exact=decode_ok, attn_decode_faulty=decode_faulty,
     )
 
 

@@ -33,6 +33,11 @@ forward with online softmax. Its fields follow those of the GEMM checks.
 ``amd.com/gpu-burn-in-attention-causal``): the same forward for many heads at
 head dimension 128 under the causal mask. Its fields follow those of
 ``--attention``.
+
+``--deep --attention-decode`` adds the decode attention check (annotation
+``amd.com/gpu-burn-in-attention-decode``): one query token a sequence over a
+paged KV cache, grouped-query heads, split-KV with a merge kernel. Its fields
+follow those of ``--attention-causal``.
 """
 from __future__ import annotations
 
@@ -80,6 +85,9 @@ def main(argv=None) -> int:
     parser.add_argument("--attention-causal", action="store_true",
                         help="with --deep: the exact causal attention check, "
                              "many heads at head dimension 128")
+    parser.add_argument("--attention-decode", action="store_true",
+                        help="with --deep: the exact decode attention check, "
+                             "paged KV cache, GQA and split-KV")
     args = parser.parse_args(argv)
     if args.gemm and not args.deep:
         parser.error("--gemm needs --deep")
@@ -89,6 +97,8 @@ def main(argv=None) -> int:
         parser.error("--attention needs --deep")
     if args.attention_causal and not args.deep:
         parser.error("--attention-causal needs --deep")
+    if args.attention_decode and not args.deep:
+        parser.error("--attention-decode needs --deep")
     if args.load_seconds and not args.deep:
         parser.error("--load-seconds needs --deep")
     if args.mfma_floor_tflops and not args.load_seconds:
@@ -118,6 +128,8 @@ def main(argv=None) -> int:
         load["attention"] = True
     if args.attention_causal:
         load["attention_causal"] = True
+    if args.attention_decode:
+        load["attention_decode"] = True
 
     try:
         if args.deep:
@@ -163,6 +175,9 @@ def main(argv=None) -> int:
             if args.attention_causal:
                 out.update(attn_causal_exact=report.attn_causal_exact,
                            attn_causal_faulty=report.attn_causal_faulty)
+            if args.attention_decode:
+                out.update(attn_decode_exact=report.attn_decode_exact,
+                           attn_decode_faulty=report.attn_decode_faulty)
             print(json.dumps(out))
         else:
             cu = (f" cu_total={report.cu_total} cu_covered={report.cu_covered} "
@@ -182,6 +197,9 @@ def main(argv=None) -> int:
             if args.attention_causal:
                 cu += (f" attn_causal_exact={report.attn_causal_exact} "
                        f"attn_causal_faulty={report.attn_causal_faulty}")
+            if args.attention_decode:
+                cu += (f" attn_decode_exact={report.attn_decode_exact} "
+                       f"attn_decode_faulty={report.attn_decode_faulty}")
             print(f"healthy={report.healthy} mfma_ok={report.mfma_ok} "
                   f"hbm_gb_s={report.hbm_gb_s} rocm_smi_ok={report.rocm_smi_ok} "
                   f"mfma_exact={report.mfma_exact} "

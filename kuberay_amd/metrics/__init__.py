@@ -189,7 +189,8 @@ class OperatorMetrics:
         # the GEMM check's, only when the report has them
         # and the attention checks'
         for field, check in (("gemm_exact", "gemm"), ("gemm_narrow_exact", "gemm"),
-                             ("attn_exact", "attn"), ("attn_causal_exact", "attn_causal")):
+                             ("attn_exact", "attn"), ("attn_causal_exact", "attn_causal"),
+                             ("attn_decode_exact", "attn_decode")):
             for dtype, ok in (getattr(report, field, None) or {}).items():
                 self.gpu_burn_in_ok.labels(node, f"{check}_{dtype}").set(1 if ok else 0)
 

@@ -257,6 +257,9 @@ GPU_BURN_IN_ATTENTION_ANNOTATION_KEY = "amd.com/gpu-burn-in-attention"
 # The same for the causal attention check at head dimension 128
 # (``--attention-causal``).
 GPU_BURN_IN_ATTENTION_CAUSAL_ANNOTATION_KEY = "amd.com/gpu-burn-in-attention-causal"
+# The same for the decode attention check: paged KV cache, GQA, split-KV
+# (``--attention-decode``).
+GPU_BURN_IN_ATTENTION_DECODE_ANNOTATION_KEY = "amd.com/gpu-burn-in-attention-decode"
 
 # Device nodes every ROCm container needs (AMD k8s device plugin mounts these
 # automatically when amd.com/gpu is requested; we also support explicit
