@@ -4,8 +4,9 @@ live next to the sources so it travels to GPU boxes with the repo snapshot).
 Extensions:
   * gpuhealth  — HIP/gfx950 on-device health probes and burn-in
                  (gpuhealth.hip, gpuhealth_gemm.hip, gpuhealth_gemm_narrow.hip,
-                 gpuhealth_attn.hip, gpuhealth_attn128.hip and
-                 gpuhealth_attn_decode.hip over gpuhealth_ref.hpp)
+                 gpuhealth_attn.hip, gpuhealth_attn128.hip,
+                 gpuhealth_attn_decode.hip and gpuhealth_moe.hip over
+                 gpuhealth_ref.hpp)
   * engine     — C++ control-plane core: object cache + indices + native
                  JSON encoding and decoding and model-tree copies (engine.cpp
                  bindings over store_core.hpp, json_decode.hpp and
@@ -48,7 +49,7 @@ def build_gpuhealth(force: bool = False) -> Path:
     src = HERE / "gpuhealth.hip"
     gemm_srcs = [HERE / "gpuhealth_gemm.hip", HERE / "gpuhealth_gemm_narrow.hip",
                  HERE / "gpuhealth_attn.hip", HERE / "gpuhealth_attn128.hip",
-                 HERE / "gpuhealth_attn_decode.hip"]
+                 HERE / "gpuhealth_attn_decode.hip", HERE / "gpuhealth_moe.hip"]
     out = HERE / f"gpuhealth{_ext_suffix()}"
     if not force and not _needs_rebuild(src, out, *gemm_srcs, HERE / "gpuhealth_ref.hpp",
                                         HERE / "gpuhealth_gemm.hpp",

@@ -257,14 +257,34 @@
 //                    attn_decode_exact(inject=) into Q, K, V or the block
 //                    table, debug_attn_decode_dump, attn_decode_operand.
 //                    Details: gpuhealth_attn_decode.hip.
+//   * moe_exact    — opt-in, single-shot, an entry point of its own: the routed
+//                    expert GEMM of a mixture-of-experts layer and its top-k
+//                    combine. Token rows gathered through an index list into
+//                    the direct-to-LDS loads, ragged expert groups (some
+//                    empty) whose tiles every workgroup finds on the device
+//                    from the offsets with a wave prefix sum, masked tail
+//                    rows next to a poison row and guard rows, expert weights
+//                    picked by a loaded value, per-entry products by plain
+//                    stores and the weighted sum a token by
+//                    global_atomic_add_f32 from several workgroups. Weights
+//                    in {1, 1/2, 1/4}: both outputs compare with == in every
+//                    order, for top_k <= 8 and k <= 4096. Default: 16
+//                    experts, top_k 2, k = n = 1024 and the tokens that give
+//                    every CU two working workgroups. Cannot show: the
+//                    activation between a layer's two GEMMs, fp8 and MXFP4
+//                    expert weights, routing computed on the device,
+//                    global_atomic_pk_add_bf16. Test hooks:
+//                    moe_exact(inject=) into X, W or the sorted token list,
+//                    debug_moe_dump, moe_operand. Details: gpuhealth_moe.hip.
 //
 // What must agree between host and device (pattern, generators, encoders,
 // reference) is in gpuhealth_ref.hpp. The kernels of gemm_exact ("Burn-in,
 // part 5") and their host code are in gpuhealth_gemm.hip, those of
 // gemm_narrow_exact ("part 6") in gpuhealth_gemm_narrow.hip and those of
 // attn_exact ("part 7") in gpuhealth_attn.hip, those of attn_causal_exact
-// ("part 8") in gpuhealth_attn128.hip and those of attn_decode_exact ("part
-// 9") in gpuhealth_attn_decode.hip, translation units of their own
+// ("part 8") in gpuhealth_attn128.hip, those of attn_decode_exact ("part 9")
+// in gpuhealth_attn_decode.hip and those of moe_exact ("part 10") in
+// gpuhealth_moe.hip, translation units of their own
 // (the reason is at the top of the first); this file binds them.
 //
 // Build: hipcc --offload-arch=gfx950 (see kuberay_amd/_native/build.py).
@@ -2902,6 +2922,121 @@ static int attn_decode_operand(const std::string& dtype, const std::string& whic
                         checked_index(col, gh::kAttn128HeadDim, "column"));
 }
 
+// -- MoE check bindings (Burn-in, part 10: gpuhealth_moe.hip) -----------------
+static int parse_moe_dtype(const std::string& dtype) {
+  const int dt = parse_dtype(dtype);
+  if (dt != gh::BF16 && dt != gh::F16)
+    throw py::value_error("the MoE check runs bf16 and f16 only");
+  return dt;
+}
+
+// (target "x", "w" or "route", row, col, xor mask): a token row of X, row
+// expert * k + row of W, or the sorted entry whose token id is xored (col 0);
+// the place is checked by run_moe_exact
+static std::optional<ghgemm::MoeInject> checked_moe_inject(const inject_attn_t& in) {
+  if (!in) return std::nullopt;
+  const auto& [target, row, col, mask] = *in;
+  ghgemm::MoeInject inj;
+  if (target == "x") inj.which = ghgemm::MOE_X;
+  else if (target == "w") inj.which = ghgemm::MOE_W;
+  else if (target == "route") inj.which = ghgemm::MOE_ROUTE;
+  else throw py::value_error("inject target must be x, w or route (got '" + target + "')");
+  inj.row = checked_index(row, 1ull << 32, "injected row");
+  inj.col = checked_index(col, 1ull << 32, "injected column");
+  inj.mask = checked_index(mask, 1ull << 32, "xor mask");
+  return inj;
+}
+
+typedef std::optional<std::vector<int64_t>> moe_route_t;
+
+// the dict of gemm_exact (k and n are the experts' K x N) plus tokens, experts,
+// top_k, entries and tiles; first_bad is over Y. A faulty tile is (row tile,
+// column tile) of a workgroup whose rows of P are bad, with the CU it ran on
+// and first_bad (sorted entry, col), or carries no CU but a place: "scatter"
+// when Y is bad over clean products, first_bad (token, col), and "guard" when
+// a word of P's guard rows is not zero, first_bad (row of P, col).
+static py::dict moe_dict(const ghgemm::MoeResult& r) {
+  py::dict d;
+  py::list faulty;
+  for (const ghgemm::FaultyTile& f : r.faulty) {
+    const bool no_cu = f.key == ghgemm::kMoeNoCu || f.key == ghgemm::kMoeGuardKey;
+    py::dict t = no_cu ? py::dict() : location_dict(f.key);
+    if (no_cu) t["place"] = f.key == ghgemm::kMoeNoCu ? "scatter" : "guard";
+    t["tile"] = py::make_tuple(f.tile_row, f.tile_col);
+    t["mismatches"] = f.stats.mismatches;
+    t["first_bad"] = py::make_tuple(f.stats.first_bad / r.n, f.stats.first_bad % r.n);
+    faulty.append(t);
+  }
+  d["dtype"] = kDtypeNames[r.dtype];
+  d["tokens"] = r.tokens;
+  d["experts"] = r.experts;
+  d["top_k"] = r.top_k;
+  d["k"] = r.k;
+  d["n"] = r.n;
+  d["entries"] = r.entries;
+  d["tiles"] = r.tiles;
+  d["ok"] = r.mismatches == 0 && r.faulty.empty();
+  d["mismatches"] = r.mismatches;
+  if (r.first_bad >= 0)
+    d["first_bad"] = py::make_tuple(r.first_bad / r.n, r.first_bad % r.n, r.got, r.expected);
+  else
+    d["first_bad"] = py::none();
+  d["faulty"] = faulty;
+  d["workgroups"] = r.workgroups;
+  d["cu_total"] = r.cu_total;
+  d["cu_seen"] = r.cu_seen;
+  d["elapsed_ms"] = r.elapsed_ms;
+  // for information: one cold launch, nothing is gated on it
+  d["tflops"] = r.elapsed_ms > 0.0
+                    ? 2.0 * r.entries * r.k * r.n / (r.elapsed_ms * 1e-3) / 1e12 : 0.0;
+  return d;
+}
+
+static py::dict moe_exact(int device, const std::string& dtype, int64_t tokens, int64_t experts,
+                          int64_t top_k, int64_t k, int64_t n, moe_route_t route, uint32_t seed,
+                          inject_attn_t inject) {
+  const int dt = parse_moe_dtype(dtype);
+  const std::optional<ghgemm::MoeInject> inj = checked_moe_inject(inject);
+  use_device(device);
+  return moe_dict(ghgemm::run_moe_exact(dt, tokens, experts, top_k, k, n,
+                                        route ? *route : std::vector<int64_t>(), seed,
+                                        inj ? &*inj : nullptr));
+}
+
+// test hook: the raw operands, the routing the kernel read and both outputs of
+// the same fill, inject and launch
+static py::dict debug_moe_dump(int device, const std::string& dtype, int64_t tokens,
+                               int64_t experts, int64_t top_k, int64_t k, int64_t n,
+                               moe_route_t route, uint32_t seed, inject_attn_t inject) {
+  const int dt = parse_moe_dtype(dtype);
+  const std::optional<ghgemm::MoeInject> inj = checked_moe_inject(inject);
+  use_device(device);
+  ghgemm::MoeDump dump;
+  (void)ghgemm::run_moe_exact(dt, tokens, experts, top_k, k, n,
+                              route ? *route : std::vector<int64_t>(), seed,
+                              inj ? &*inj : nullptr, &dump);
+  py::dict d;
+  d["x"] = py::bytes(dump.x);
+  d["w"] = py::bytes(dump.w);
+  d["offsets"] = py::bytes(dump.offsets);
+  d["sorted_token"] = py::bytes(dump.sorted_token);
+  d["sorted_weight"] = py::bytes(dump.sorted_weight);
+  d["p"] = py::bytes(dump.p);
+  d["y"] = py::bytes(dump.y);
+  return d;
+}
+
+// X at its token row, W at row expert * k + row
+static int moe_operand(const std::string& dtype, const std::string& which, int64_t row,
+                       int64_t col, uint32_t seed) {
+  const int dt = parse_moe_dtype(dtype);
+  if (which != "x" && which != "w")
+    throw py::value_error("which must be x or w (got '" + which + "')");
+  return gh::gen_moe(seed, dt, which == "x" ? gh::GEN_A : gh::GEN_B,
+                     checked_index(row, 1ull << 32, "row"),
+                     checked_index(col, 1ull << 32, "column"));
+}
+
 static std::vector<std::vector<int>> debug_permlane_dump(int device) {
   use_device(device);
   return ghgemm::run_debug_permlane_dump();
@@ -3061,6 +3196,19 @@ PYBIND11_MODULE(gpuhealth, m) {
         py::arg("inject") = py::none());
   m.def("attn_decode_operand", &attn_decode_operand, py::arg("dtype"), py::arg("which"),
         py::arg("row"), py::arg("col"), py::arg("seed") = gh::kDefaultSeed);
+  m.attr("MOE_MAX_K") = gh::kMoeMaxK;
+  m.attr("MOE_MAX_TOP_K") = gh::kMoeMaxTopK;
+  m.attr("MOE_POISON") = gh::kMoePoison;
+  m.def("moe_exact", &moe_exact, py::arg("device") = 0, py::arg("dtype") = "bf16",
+        py::arg("tokens") = 0, py::arg("experts") = 0, py::arg("top_k") = 0, py::arg("k") = 0,
+        py::arg("n") = 0, py::arg("route") = py::none(), py::arg("seed") = gh::kDefaultSeed,
+        py::arg("inject") = py::none());
+  m.def("debug_moe_dump", &debug_moe_dump, py::arg("device") = 0, py::arg("dtype") = "bf16",
+        py::arg("tokens") = 0, py::arg("experts") = 0, py::arg("top_k") = 0, py::arg("k") = 0,
+        py::arg("n") = 0, py::arg("route") = py::none(), py::arg("seed") = gh::kDefaultSeed,
+        py::arg("inject") = py::none());
+  m.def("moe_operand", &moe_operand, py::arg("dtype"), py::arg("which"), py::arg("row"),
+        py::arg("col"), py::arg("seed") = gh::kDefaultSeed);
   m.def("debug_permlane_dump", &debug_permlane_dump, py::arg("device") = 0);
   m.def("debug_exp2_dump", &debug_exp2_dump, py::arg("device") = 0);
   m.def("flop_per_mfma", [](const std::string& dtype) {

@@ -1,7 +1,7 @@
 // gpuhealth_gemm — what gpuhealth.hip (bindings) and gpuhealth_gemm.hip
 // (kernels and their host code) share of the burn-in's GEMM check, and below
 // that what it shares with gpuhealth_gemm_narrow.hip, gpuhealth_attn.hip,
-// gpuhealth_attn128.hip and gpuhealth_attn_decode.hip: plain
+// gpuhealth_attn128.hip, gpuhealth_attn_decode.hip and gpuhealth_moe.hip: plain
 // structs and a few functions, no HIP and no pybind11 types. The files are
 // separate translation units so that the GEMM kernels can be compiled with a
 // switch of their own (kuberay_amd/_native/build.py) while every older kernel
@@ -218,5 +218,64 @@ DecodeResult run_attn_decode_exact(int dtype, int64_t batch, int64_t kv_heads, i
                                    const std::vector<int64_t>& ctx, uint32_t seed,
                                    const AttnInject* inject = nullptr,
                                    DecodeDump* dump = nullptr);
+
+// --- the MoE check: routed grouped GEMM, atomic scatter-add (gpuhealth_moe.hip) --
+
+constexpr uint32_t kMoeDefaultExperts = 16;
+constexpr uint32_t kMoeDefaultTopK = 2;
+// the place of a faulty tile that is no workgroup: Y is bad over clean products
+constexpr uint32_t kMoeNoCu = kDecodeNoCu;
+// and of the one that stands for P's guard rows when a word of them is not zero
+constexpr uint32_t kMoeGuardKey = ~0u - 2u;
+
+enum MoeTarget : int { MOE_X = 0, MOE_W = 1, MOE_ROUTE = 2 };
+
+// Test hook: an xor in device memory between the fill and the launch. MOE_X:
+// the 16-bit element (token row, col) of X; MOE_W: element (expert · K + row,
+// col) of W; MOE_ROUTE: the token id of sorted entry `row` (col 0), with a
+// non-zero mask whose result stays below T, so that the kernel gathers and
+// scatters a wrong token inside the batch.
+struct MoeInject {
+  int which = MOE_X;
+  uint32_t row = 0, col = 0, mask = 0;
+};
+
+struct MoeResult : Result {
+  uint32_t tokens = 0, experts = 0, top_k = 0, entries = 0;
+  uint32_t tiles = 0;  // row tiles that found an expert, from where[]
+};
+
+struct MoeDump {
+  std::string x, w, offsets, sorted_token, sorted_weight, p, y;
+};
+
+// The routed expert GEMM of a mixture-of-experts layer on the current device:
+// X [tokens + 1, k] (the last row poison), W [experts, k, n], every token to
+// top_k distinct experts with a weight in {1, 1/2, 1/4}; P [entries + 64, n]
+// holds the unweighted products in sorted-entry order, Y [tokens + 1, n] the
+// weighted sums, added by fp32 atomics. `route` is tokens · top_k expert ids,
+// token-major, or empty for gh::moe_default_expert. 0 takes the default:
+// experts = 16, top_k = 2, k = n = 1024, tokens = the length of route / top_k
+// or, route being empty, the smallest multiple of 64 at which the generated
+// routing gives every CU kWorkgroupsPerCu workgroups that find a tile; a shape
+// that cannot do so up to gh::kMoeMaxTokens has no default and needs tokens.
+// In the Result m is tokens; first_bad (row * n + col) is over Y, guard row
+// included, and mismatches counts Y plus every non-zero word of P's guard
+// rows; workgroups counts those that found a tile. A faulty tile is (row tile,
+// column tile) for a workgroup whose rows of P are bad, (0, 0) with key
+// kMoeNoCu when Y is bad while every P is clean: the scatter, and (one past
+// the grid's row tiles, 0) with key kMoeGuardKey for dirty guard rows of P,
+// its first_bad being row of P * n + col. Throws
+// std::invalid_argument for a data type other than bf16 / f16, k or n that is
+// no positive multiple of 64, k above gh::kMoeMaxK (exactness), n above
+// gh::kGemmMaxMN, experts outside 1 .. 64, top_k outside 1 .. min(8, experts),
+// tokens below 1, above gh::kMoeMaxTokens or needing more than
+// gh::kMoeMaxBytes, a route of the wrong length, with an id out of range or
+// with an expert twice in a token, and an inject outside its target, with a
+// mask that is zero or wider than 16 bits or, for the route, with a result
+// that is no token; std::runtime_error for a failing HIP call.
+MoeResult run_moe_exact(int dtype, int64_t tokens, int64_t experts, int64_t top_k, int64_t k,
+                        int64_t n, const std::vector<int64_t>& route, uint32_t seed,
+                        const MoeInject* inject = nullptr, MoeDump* dump = nullptr);
 
 }  // namespace ghgemm

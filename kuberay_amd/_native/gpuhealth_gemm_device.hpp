@@ -1,6 +1,7 @@
 // gpuhealth_gemm_device — what the translation units of the burn-in's GEMM and
 // attention checks (gpuhealth_gemm.hip, gpuhealth_gemm_narrow.hip,
-// gpuhealth_attn.hip, gpuhealth_attn128.hip, gpuhealth_attn_decode.hip) share on the HIP side:
+// gpuhealth_attn.hip, gpuhealth_attn128.hip, gpuhealth_attn_decode.hip,
+// gpuhealth_moe.hip) share on the HIP side:
 // the error check, the scope that frees device memory, the hardware-register
 // reads of the location key and the result bookkeeping. Not for gpuhealth.hip.
 #pragma once

@@ -7,10 +7,12 @@
 // exact reference product, the matrix generator and reference of the GEMM
 // checks, and the generators, the premise, the integer reference and the LDS
 // address functions of the attention check, of the causal one at head
-// dimension 128 and of the paged decode one. No HIP, no pybind11 — the programs
-// under tests/native/ (gpuhealth_ref_check.cpp, gemm_ref_check.cpp,
-// gemm_narrow_ref_check.cpp, attn_ref_check.cpp, attn128_ref_check.cpp,
-// attn_decode_ref_check.cpp) drive it as stand-alone g++ programs.
+// dimension 128 and of the paged decode one, and the generators, the routing
+// builder, the tile lookup and the reference of the MoE check. No HIP, no
+// pybind11 — the programs under tests/native/ (gpuhealth_ref_check.cpp,
+// gemm_ref_check.cpp, gemm_narrow_ref_check.cpp, attn_ref_check.cpp,
+// attn128_ref_check.cpp, attn_decode_ref_check.cpp, moe_ref_check.cpp) drive it
+// as stand-alone g++ programs.
 //
 // Exactness premise: bf16 / f16 / fp8 operands are integers in [-8, 8], so a
 // K=32 dot product plus C is an integer below 2^12; MXFP4 operands are e2m1
@@ -1144,6 +1146,148 @@ GH_HD inline uint32_t decode_epi_o(uint32_t wave, uint32_t d, uint32_t i) {
 }
 GH_HD inline uint32_t decode_epi_ml(uint32_t wave, uint32_t which, uint32_t i) {  // 0: m, 1: l
   return wave * kDecodeWaveBytes + kDecodeStageBytes + 64u * which + 4u * i;
+}
+
+// ---------------------------------------------------------------------------
+// MoE check: a routed grouped GEMM with a top-k combine by fp32 atomics
+//
+// Tokens X are [T + 1, K] and expert weights W are [E, K, N], 16-bit, each
+// expert row-major K x N. Token t goes to top_k distinct experts route[t][j],
+// j = 0 .. top_k - 1, with the router weight moe_weight_of(seed, t, j) in
+// {1, 1/2, 1/4}. The routing the kernel reads is sorted by expert
+// (moe_build_routing): offsets[E + 1], and for entry p = offsets[e] .. of
+// expert e, tokens ascending, sorted_token[p] and sorted_weight[p]. It is input
+// data that the host builds and uploads, as the decode check's block table is.
+//   P[p][n] = Σ_k X[sorted_token[p]][k] · W[e][k][n]      (plain stores)
+//   Y[t][n] = Σ_j weight(t, j) · P[entry of (t, j)][n]    (fp32 atomics onto zero)
+//
+// Generators: X[t][k] = gemm_int_of under GEN_A at (t, k), W[e][k][n] =
+// gemm_int_of under GEN_B at (e·K + k, n): integers in [-8, 8]. Row T of X is
+// the poison row, kMoePoison = 0x7700 in every element (28672 as f16, 2^111 as
+// bf16: finite, and a K <= 4096 dot product with |w| <= 8 stays finite). The
+// tail rows of a group's last tile gather it and are masked out of P and Y, so
+// a mask that is off shows as a mismatch; row T of Y and the kMoeGuardRows rows
+// of P after the last entry are guards that must stay zero, which is where a
+// row that escapes the mask lands instead of out of bounds.
+//
+// Exactness premise. |P| <= 64 K, an integer. Every partial sum of a row of Y
+// is a multiple of 1/4 of magnitude at most top_k · 64 K; with top_k <=
+// kMoeMaxTopK = 8 and K <= kMoeMaxK = 4096 that is at most 2^21, below 2^23
+// quarters: it fits the fp32 significand, the products weight · P are exact
+// (a power of two times an integer), and the atomics give the same value in
+// every order. Shown on the device for the hashed data at the bound
+// (tests/test_gpu_moe.py); for other data argued from the bound.
+// ---------------------------------------------------------------------------
+constexpr uint32_t kMoeMaxK = 4096;      // 8 · 64 K · 4 <= 2^23
+constexpr uint32_t kMoeMaxTopK = 8;
+constexpr uint32_t kMoeMaxExperts = 64;  // one lane an expert in the tile lookup
+constexpr uint32_t kMoePoison = 0x7700u;
+constexpr uint32_t kMoeGuardRows = kGemmTile;
+// not needed for exactness: bound what one call allocates
+constexpr uint32_t kMoeMaxTokens = 1u << 16;
+constexpr uint64_t kMoeMaxBytes = 1ull << 31;  // X, W, P and Y together
+// where[] of a workgroup past the last tile; a key never written stays ~0
+constexpr uint32_t kMoeIdleKey = 0xFFFFFFFEu;
+
+// X[row][col] at row = token, W[e][k][col] at row = e·K + k; which is GEN_A or GEN_B
+GH_HD inline int gen_moe(uint32_t seed, int dtype, uint32_t which, uint32_t row, uint32_t col) {
+  return gen_gemm_int(seed, dtype, which, row, col);
+}
+// log2 of 1 / weight: 0, 1 or 2
+GH_HD inline uint32_t moe_weight_shift(uint32_t seed, uint32_t token, uint32_t j) {
+  return mix32(mix32(seed ^ 0x30E30Eu) + token * kMoeMaxTopK + j) % 3u;
+}
+GH_HD inline float moe_weight_of(uint32_t seed, uint32_t token, uint32_t j) {
+  return 1.0f / (float)(1u << moe_weight_shift(seed, token, j));
+}
+
+// The generated routing. Experts e with e % 4 == 1 get no token where the
+// others are enough for top_k (at E = 16: 1, 5, 9 and 13 are empty, first,
+// middle and near the end); active expert a is a + (a + 2) / 3. A token's
+// first choice is the smaller of two hashed draws, so low experts carry more
+// load, and choice j is the j-th active expert after it, cyclically: distinct.
+GH_HD inline uint32_t moe_active_experts(uint32_t E, uint32_t top_k) {
+  const uint32_t na = E - (E + 2u) / 4u;
+  return na >= top_k ? na : E;
+}
+GH_HD inline uint32_t moe_default_expert(uint32_t seed, uint32_t E, uint32_t top_k, uint32_t token,
+                                         uint32_t j) {
+  const uint32_t na = moe_active_experts(E, top_k);
+  const uint32_t h = mix32(mix32(seed ^ 0x0E7E27u) + token);
+  const uint32_t d0 = (h & 0xFFFFu) % na, d1 = (h >> 16) % na;
+  const uint32_t a = ((d0 < d1 ? d0 : d1) + j) % na;
+  return na == E ? a : a + (a + 2u) / 3u;
+}
+
+// Sorts route[T · top_k] (expert of (t, j) at t · top_k + j) by expert, tokens
+// ascending within one: offsets[E + 1], sorted_token, sorted_weight and
+// entry_of[T · top_k], the entry of (t, j). The caller has checked the ids.
+inline void moe_build_routing(uint32_t seed, uint32_t T, uint32_t E, uint32_t top_k,
+                              const uint32_t* route, uint32_t* offsets, uint32_t* sorted_token,
+                              float* sorted_weight, uint32_t* entry_of) {
+  for (uint32_t e = 0; e <= E; ++e) offsets[e] = 0;
+  for (uint32_t p = 0; p < T * top_k; ++p) offsets[route[p] + 1] += 1;
+  for (uint32_t e = 0; e < E; ++e) offsets[e + 1] += offsets[e];
+  for (uint32_t p = 0; p < T * top_k; ++p) {  // offsets[e] is the cursor of group e
+    const uint32_t at = offsets[route[p]]++;
+    sorted_token[at] = p / top_k;
+    sorted_weight[at] = moe_weight_of(seed, p / top_k, p % top_k);
+    entry_of[p] = at;
+  }
+  // every cursor stands at its group's end, the start of the next one
+  for (uint32_t e = E; e > 0; --e) offsets[e] = offsets[e - 1];
+  offsets[0] = 0;
+}
+
+// The tile lookup, as the kernel does it with one lane an expert: row tile rt
+// of the grid belongs to the expert whose running count of ceil(size / 64)
+// first exceeds rt; empty experts count nothing. false past the last tile.
+GH_HD inline uint32_t moe_tiles_of(uint32_t count) { return (count + kGemmTile - 1u) / kGemmTile; }
+GH_HD inline bool moe_tile_lookup(const uint32_t* offsets, uint32_t E, uint32_t rt,
+                                  uint32_t* expert, uint32_t* first_row) {
+  uint32_t before = 0;
+  for (uint32_t e = 0; e < E; ++e) {
+    const uint32_t mine = moe_tiles_of(offsets[e + 1] - offsets[e]);
+    if (rt < before + mine) {
+      *expert = e, *first_row = offsets[e] + (rt - before) * kGemmTile;
+      return true;
+    }
+    before += mine;
+  }
+  return false;
+}
+// its inverse for an entry of expert e, and the number of non-idle row tiles
+GH_HD inline uint32_t moe_tile_of_entry(const uint32_t* offsets, uint32_t e, uint32_t entry) {
+  uint32_t before = 0;
+  for (uint32_t x = 0; x < e; ++x) before += moe_tiles_of(offsets[x + 1] - offsets[x]);
+  return before + (entry - offsets[e]) / kGemmTile;
+}
+GH_HD inline uint32_t moe_row_tiles(const uint32_t* offsets, uint32_t E) {
+  return moe_tile_of_entry(offsets, E, offsets[E]);
+}
+// what the grid is sized by: it depends on T, top_k and E alone
+GH_HD inline uint32_t moe_max_row_tiles(uint32_t T, uint32_t top_k, uint32_t E) {
+  return moe_tiles_of(T * top_k) + E;
+}
+
+// P of (token, expert) at column col, in integer arithmetic only
+GH_HD inline int32_t moe_product_element(uint32_t seed, int dtype, uint32_t K, uint32_t token,
+                                         uint32_t expert, uint32_t col) {
+  const uint32_t hx = mix32(gemm_matrix_hash(seed, dtype, GEN_A) ^ token);  // the row hoisted
+  const uint32_t hw = gemm_matrix_hash(seed, dtype, GEN_B);
+  int32_t acc = 0;
+  for (uint32_t k = 0; k < K; ++k)
+    acc += ((int)((mix32(hx + k) >> 8) % 17u) - 8) * gemm_int_of(hw, expert * K + k, col);
+  return acc;
+}
+// Y[token][col] in quarters; experts is route + token · top_k
+GH_HD inline int32_t moe_y_quarters(uint32_t seed, int dtype, uint32_t K, uint32_t top_k,
+                                    const uint32_t* experts, uint32_t token, uint32_t col) {
+  int32_t quarters = 0;
+  for (uint32_t j = 0; j < top_k; ++j)
+    quarters += moe_product_element(seed, dtype, K, token, experts[j], col) *
+                (int32_t)(4u >> moe_weight_shift(seed, token, j));
+  return quarters;
 }
 
 }  // namespace gh

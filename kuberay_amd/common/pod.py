@@ -378,7 +378,8 @@ def init_gpu_burn_in_startup_probe(ray_container: Container,
                                    gemm_narrow: bool = False,
                                    attention: bool = False,
                                    attention_causal: bool = False,
-                                   attention_decode: bool = False) -> None:
+                                   attention_decode: bool = False,
+                                   moe: bool = False) -> None:
     """MI355X burn-in as a startupProbe (opt-in, annotation
     ``amd.com/gpu-burn-in: "true"`` on a GPU worker template): the HBM
     pattern sweep and the exact MFMA checks of
@@ -406,7 +407,11 @@ def init_gpu_burn_in_startup_probe(ray_container: Container,
     decode attention check (paged KV cache, GQA, split-KV) after that one; its
     two runs took 2 ms of wall time each, burn-ins with it took 8.03 s and
     8.05 s against 8.03 s without in the same process, and the timeout stays
-    (docs/benchmarks.md, "Decode attention check").
+    (docs/benchmarks.md, "Decode attention check"). ``moe`` (annotation
+    ``amd.com/gpu-burn-in-moe: "true"``) adds the MoE check (routed grouped
+    GEMM, fp32 atomic scatter-add) last; its two runs took 1.9 ms of wall time
+    each, burn-ins with it took 8.030 s to 8.036 s against 8.030 s without in
+    the same process, and the timeout stays (docs/benchmarks.md, "MoE check").
     A user-supplied startupProbe is kept."""
     if ray_container.startup_probe is not None:
         return
@@ -425,6 +430,8 @@ def init_gpu_burn_in_startup_probe(ray_container: Container,
         command += " --attention-causal"
     if attention_decode:
         command += " --attention-decode"
+    if moe:
+        command += " --moe"
     probe = Probe(
         timeout_seconds=timeout,
         period_seconds=C.GPU_BURN_IN_PROBE_PERIOD_SECONDS,
@@ -871,7 +878,9 @@ def build_pod(
                 attention_causal=(template.metadata.annotations or {}).get(
                     C.GPU_BURN_IN_ATTENTION_CAUSAL_ANNOTATION_KEY, "").lower() == "true",
                 attention_decode=(template.metadata.annotations or {}).get(
-                    C.GPU_BURN_IN_ATTENTION_DECODE_ANNOTATION_KEY, "").lower() == "true")
+                    C.GPU_BURN_IN_ATTENTION_DECODE_ANNOTATION_KEY, "").lower() == "true",
+                moe=(template.metadata.annotations or {}).get(
+                    C.GPU_BURN_IN_MOE_ANNOTATION_KEY, "").lower() == "true")
     return pod
 
 

@@ -78,6 +78,9 @@ class HealthReport:
     # decode attention check (paged KV, GQA, split-KV); None unless asked for
     attn_decode_exact: Optional[Dict[str, bool]] = None
     attn_decode_faulty: Optional[List[str]] = None
+    # MoE check (routed grouped GEMM, atomic scatter-add); None unless asked for
+    moe_exact: Optional[Dict[str, bool]] = None
+    moe_faulty: Optional[List[str]] = None
 
 
 def _rocm_smi_ok() -> bool:
@@ -137,8 +140,8 @@ DEFAULT_BURN_IN_HBM_FRACTION = 0.9
 
 
 def _cu_name(where, short: bool = False) -> str:
-    if "cu" not in where:  # the decode check's merge over splits: a kernel, no one CU
-        return "merge"
+    if "cu" not in where:  # no one CU: the decode check's merge over splits, or
+        return where.get("place", "merge")  # the MoE check's scatter-add or guard rows
     if short:
         return f"xcc{where['xcc']}/se{where['se']}/cu{where['cu']}"
     return f"xcc{where['xcc']}/se{where['se']}/sh{where['sh']}/cu{where['cu']}"
@@ -209,11 +212,12 @@ def _gemm_exact(native, device: int, entry: str = "gemm_exact", dtypes=GEMM_DTYP
     dimension where the GEMM's has k; with ``entry="attn_causal_exact"`` the
     causal one, whose shape is heads x seq x head dimension; with
     ``entry="attn_decode_exact"`` the decode one, whose shape is batch x
-    kv_heads x group and the context. Returns (ok by data type, faulty,
-    problems)."""
+    kv_heads x group and the context; with ``entry="moe_exact"`` the MoE
+    check, whose shape is tokens x experts, top_k and the experts' k x n.
+    Returns (ok by data type, faulty, problems)."""
     what = {"gemm_exact": "gemm", "gemm_narrow_exact": "gemm narrow",
             "attn_exact": "attention", "attn_causal_exact": "attention causal",
-            "attn_decode_exact": "attention decode"}[entry]
+            "attn_decode_exact": "attention decode", "moe_exact": "moe"}[entry]
     if not hasattr(native, entry):
         return {}, [], [f"{what}: asked for, but this native module has no {entry}"]
     ok, faulty, problems = {}, [], []
@@ -229,6 +233,9 @@ def _gemm_exact(native, device: int, entry: str = "gemm_exact", dtypes=GEMM_DTYP
         elif entry == "attn_decode_exact":  # rows flat: (sequence, KV head, query head)
             problem = (f"attention decode {dtype} {r['batch']}x{r['kv_heads']}x{r['group']} "
                        f"ctx {r['max_ctx']}: {r['mismatches']} bad elements")
+        elif entry == "moe_exact":  # rows are tokens of Y
+            problem = (f"moe {dtype} {r['tokens']}x{r['experts']} top{r['top_k']} "
+                       f"{r['k']}x{r['n']}: {r['mismatches']} bad elements")
         else:
             depth = r["head_dim"] if entry == "attn_exact" else r["k"]
             problem = (f"{'attention' if entry == 'attn_exact' else 'gemm'} {dtype} "
@@ -254,7 +261,8 @@ def check_gpu_burn_in(device: int = 0,
                       gemm_narrow: bool = False,
                       attention: bool = False,
                       attention_causal: bool = False,
-                      attention_decode: bool = False) -> HealthReport:
+                      attention_decode: bool = False,
+                      moe: bool = False) -> HealthReport:
     """Burn-in level: the full gate of ``check_gpu_health``, then the exact
     MFMA verification on the bf16, f16, fp8 and MXFP4 data paths, then a
     data-verifying pattern sweep over ``hbm_fraction`` of the free HBM, then
@@ -288,6 +296,11 @@ def check_gpu_burn_in(device: int = 0,
     grouped-query heads, the context split over workgroups and merged by a
     second kernel; reported alike over the flat rows (sequence x kv_heads + KV
     head) x group + query head, a bad merge being named ``merge`` for a CU.
+    With ``moe`` the MoE check follows that one: token rows gathered through an
+    index list, ragged expert groups whose tiles are found on the device,
+    per-entry products and their weighted sums by fp32 atomics; reported alike
+    over the rows of the summed output, sums that are bad over clean products
+    being named ``scatter`` for a CU.
     Raises GpuHealthError on non-GPU hosts; ``detail`` names what failed."""
     if not gpu_node():
         raise GpuHealthError("not a GPU node (/dev/kfd missing)")
@@ -383,6 +396,14 @@ def check_gpu_burn_in(device: int = 0,
             return _hip_failure(e, rocm_ok)
         problems.extend(decode_problems)
         healthy = healthy and not decode_problems
+    moe_ok = moe_faulty = None
+    if moe:
+        try:
+            moe_ok, moe_faulty, moe_problems = _gemm_exact(native, device, "moe_exact")
+        except RuntimeError as e:
+            return _hip_failure(e, rocm_ok)
+        problems.extend(moe_problems)
+        healthy = healthy and not moe_problems
     load_ok = load_by_dtype = load_tflops = load_clock = load_faulty = None
     if load_seconds > 0.0:
         try:
@@ -414,6 +435,7 @@ def check_gpu_burn_in(device: int = 0,
         attn_exact=attn_ok, attn_faulty=attn_faulty,
         attn_causal_exact=causal_ok, attn_causal_faulty=causal_faulty,
         attn_decode_exact=decode_ok, attn_decode_faulty=decode_faulty,
+        moe_exact=moe_ok, moe_faulty=moe_faulty,
     )
 
 

@@ -38,6 +38,10 @@ head dimension 128 under the causal mask. Its fields follow those of
 ``amd.com/gpu-burn-in-attention-decode``): one query token a sequence over a
 paged KV cache, grouped-query heads, split-KV with a merge kernel. Its fields
 follow those of ``--attention-causal``.
+
+``--deep --moe`` adds the MoE check (annotation ``amd.com/gpu-burn-in-moe``):
+the routed grouped GEMM of a mixture-of-experts layer with its top-k combine
+by fp32 atomics. Its fields follow those of ``--attention-decode``.
 """
 from __future__ import annotations
 
@@ -88,6 +92,9 @@ def main(argv=None) -> int:
     parser.add_argument("--attention-decode", action="store_true",
                         help="with --deep: the exact decode attention check, "
                              "paged KV cache, GQA and split-KV")
+    parser.add_argument("--moe", action="store_true",
+                        help="with --deep: the exact MoE check, routed grouped "
+                             "GEMM and atomic scatter-add")
     args = parser.parse_args(argv)
     if args.gemm and not args.deep:
         parser.error("--gemm needs --deep")
@@ -99,6 +106,8 @@ def main(argv=None) -> int:
         parser.error("--attention-causal needs --deep")
     if args.attention_decode and not args.deep:
         parser.error("--attention-decode needs --deep")
+    if args.moe and not args.deep:
+        parser.error("--moe needs --deep")
     if args.load_seconds and not args.deep:
         parser.error("--load-seconds needs --deep")
     if args.mfma_floor_tflops and not args.load_seconds:
@@ -130,6 +139,8 @@ def main(argv=None) -> int:
         load["attention_causal"] = True
     if args.attention_decode:
         load["attention_decode"] = True
+    if args.moe:
+        load["moe"] = True
 
     try:
         if args.deep:
@@ -178,6 +189,8 @@ def main(argv=None) -> int:
             if args.attention_decode:
                 out.update(attn_decode_exact=report.attn_decode_exact,
                            attn_decode_faulty=report.attn_decode_faulty)
+            if args.moe:
+                out.update(moe_exact=report.moe_exact, moe_faulty=report.moe_faulty)
             print(json.dumps(out))
         else:
             cu = (f" cu_total={report.cu_total} cu_covered={report.cu_covered} "
@@ -200,6 +213,8 @@ def main(argv=None) -> int:
             if args.attention_decode:
                 cu += (f" attn_decode_exact={report.attn_decode_exact} "
                        f"attn_decode_faulty={report.attn_decode_faulty}")
+            if args.moe:
+                cu += f" moe_exact={report.moe_exact} moe_faulty={report.moe_faulty}"
             print(f"healthy={report.healthy} mfma_ok={report.mfma_ok} "
                   f"hbm_gb_s={report.hbm_gb_s} rocm_smi_ok={report.rocm_smi_ok} "
                   f"mfma_exact={report.mfma_exact} "

@@ -190,7 +190,7 @@ class OperatorMetrics:
         # and the attention checks'
         for field, check in (("gemm_exact", "gemm"), ("gemm_narrow_exact", "gemm"),
                              ("attn_exact", "attn"), ("attn_causal_exact", "attn_causal"),
-                             ("attn_decode_exact", "attn_decode")):
+                             ("attn_decode_exact", "attn_decode"), ("moe_exact", "moe")):
             for dtype, ok in (getattr(report, field, None) or {}).items():
                 self.gpu_burn_in_ok.labels(node, f"{check}_{dtype}").set(1 if ok else 0)
 

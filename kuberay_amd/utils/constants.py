@@ -260,6 +260,8 @@ GPU_BURN_IN_ATTENTION_CAUSAL_ANNOTATION_KEY = "amd.com/gpu-burn-in-attention-cau
 # The same for the decode attention check: paged KV cache, GQA, split-KV
 # (``--attention-decode``).
 GPU_BURN_IN_ATTENTION_DECODE_ANNOTATION_KEY = "amd.com/gpu-burn-in-attention-decode"
+# The same for the MoE check: routed grouped GEMM, atomic scatter-add (``--moe``).
+GPU_BURN_IN_MOE_ANNOTATION_KEY = "amd.com/gpu-burn-in-moe"
 
 # Device nodes every ROCm container needs (AMD k8s device plugin mounts these
 # automatically when amd.com/gpu is requested; we also support explicit
